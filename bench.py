@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the stereo matching hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
                     [--workload north_star|cones|cv|c3|c4|c5|north_star_sgm|cones_sgm]
                     [--mode auto|pairdp|dshard|dshard_rep|rowband] [--no-cpu-baseline] [--dump-disp PATH]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line
+(`value`, `ms_per_step`).  Everything else -- per-stage and per-kernel times, the roofline, the
+precision / parity / host-I/O checks, the reference's GPU path and BASELINE config 3 beside the line,
+the other multi-GPU schemes and the CPU baselines -- takes runs of its own and is behind --full
+(--no-cpu-baseline and --no-c3 trim a --full run).
 
 A step = one stereo pair through the hot path with inputs resident in HBM:
 u8 images -> z-norm + pad -> MC-CNN-fast tower (5 conv layers, f16x3 MFMA at fp32
@@ -12,8 +18,8 @@ accuracy) on both images -> fused certified cost volume + WTA over D disparities
 Default workload: the north-star size 1024x1024, D = 192 (BASELINE.json).
 
 N > 1 (one process per GPU under torchrun, RCCL).  The default --mode auto runs dshard (the north
-star's disparity-sharded cost volume) for `value` on the tower + CV/WTA workloads and times the other
-three schemes on the same pair after it (stages.multi_gpu_modes); on the SGM workloads (c3,
+star's disparity-sharded cost volume) for `value` on the tower + CV/WTA workloads and, with --full, times
+the other three schemes on the same pair after it (stages.multi_gpu_modes); on the SGM workloads (c3,
 north_star_sgm: every SGM step needs all D) it runs pairdp:
   pairdp : every rank matches its own pair each step (config 4) -- weak scaling,
            no collective on the data path;
@@ -140,7 +146,7 @@ TOWER_ARITH = {
 def make_step(m: StereoMatcher, what: str, t_conv: Timer, t_cv: Timer, t_tower: Timer):
     """One pass of the hot path.  The tower runs through the shipped StereoMatcher.features with a
     launch hook (pipeline.tower_steps: the same launches and bits as the one-call
-    sde_tower_forward_batch, checked in main), so single kernels can be timed."""
+    sde_tower_forward_batch, checked by --full), so single kernels can be timed."""
     if what == "tower+cbca+sgm":
         def step_sgm(timed=None):
             e = t_tower.start() if timed == "stages" else None
@@ -161,8 +167,9 @@ def make_step(m: StereoMatcher, what: str, t_conv: Timer, t_cv: Timer, t_tower: 
             t_conv.stop(e)
 
     def step(timed=None):
-        """timed: None (warm-up), "conv" (the timed region: HIP events around the roofline kernel
-        only) or "stages" (after the timed region: events around the tower and the CV+WTA)."""
+        """timed: None (warm-up and the timed region: no events) or, after the timed region of a
+        --full run, "conv" (HIP events around the roofline kernel only) or "stages" (events around
+        the tower and the CV+WTA)."""
         if what == "tower+cv_wta":
             e_t = t_tower.start() if timed == "stages" else None
             m.features(on_launch=conv_hook if timed == "conv" else (lambda layer, launch: launch()))
@@ -494,94 +501,22 @@ def make_mode(mode, H, W, D, what, rank, world, args, t_conv, t_cv, t_tower):
     return step, 1, "strong", f"{mode}{world}", lambda: obj.disp
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)     # ~0.1 s timed at the north star: 10 steps (20 ms) swung 2.05-2.25 ms/pair box to box
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--workload", default="north_star", choices=sorted(WORKLOADS))
-    ap.add_argument("--mode", default="auto", choices=["auto", "pairdp", "dshard", "dshard_rep", "rowband"])
-    ap.add_argument("--dump-disp", default=None, help="rank 0 saves the disparity map (.npy; auto mode: also "
-                                                         "<path>.<mode>.npy for every other scheme)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c3", action="store_true", help="north_star: skip stages.c3 (BASELINE config 3 timed "
-                                                         "beside the line)")
-    ap.add_argument("--tower-precision", default="f16x3", choices=["fp32", "bf16x6", "f16x3", "f16x3w", "f16x3m32"])
-    ap.add_argument("--cv-mode", default="certified", choices=["certified", "exact"])
-    args = ap.parse_args()
+def dump_outputs(outdir, out):
+    """--dump-outputs: what the last timed step returned -- the disparity map(s) its caller receives --
+    as float32 DIR/<name>.npy (the largest workload's maps are 48 MB together)."""
+    maps = out if isinstance(out, (tuple, list)) else (out,)
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in zip(("disparity", "disparity_right"), maps):
+        np.save(os.path.join(outdir, name + ".npy"), t.detach().cpu().numpy().astype(np.float32, copy=False))
 
-    rank, world, local = init_from_env()
-    if world != args.gpus and rank == 0:
-        print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
-    # (init_from_env selected the device: cuda:LOCAL_RANK, or LOCAL_RANK mod the device count for
-    # ranks sharing a GPU over gloo)
-    H, W, D, what = WORKLOADS[args.workload]
-    left, right, _ = stereo_pair(H, W, D, seed=rank)     # this rank's pair (pair-DP; rank 0: seed 0)
-    mode = resolve_mode(args.mode, world, what)
 
-    t_conv, t_cv, t_tower = Timer(), Timer(), Timer()
-    m = None
-    step, pairs_per_step, scaling, par, result = make_mode(mode, H, W, D, what, rank, world, args,
-                                                           t_conv, t_cv, t_tower)
-    if mode == "pairdp":
-        m = step.matcher
-
-    def timed_run(step_fn, nsteps, nwarm, timed):
-        for _ in range(nwarm):
-            step_fn()
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(nsteps):
-            step_fn(timed=timed)
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        torch.cuda.synchronize()
-        el = time.perf_counter() - t0
-        # max over ranks (gloo reduces host tensors: SDE_DIST_BACKEND=gloo runs ranks on a shared GPU)
-        tt = torch.tensor([el], dtype=torch.float64,
-                          device="cuda" if world == 1 or dist.get_backend() == "nccl" else "cpu")
-        if world > 1:
-            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        return float(tt.item())
-
-    elapsed = timed_run(step, args.steps, args.warmup, "conv")
-    # per-stage times from a few extra steps outside the timed region (their events would add
-    # stream barriers to the timed steps)
-    for _ in range(min(args.steps, 5)):
-        step(timed="stages")
-    torch.cuda.synchronize()
-    disp_primary = result().detach().clone() if args.dump_disp else None
-
-    multi = None
-    if world > 1 and args.mode == "auto" and what == "tower+cv_wta":
-        # the other multi-GPU schemes on the same pair, same ranks, same clock discipline (barrier +
-        # max over ranks); pair-DP is weak scaling (world pairs per step), the rest strong (one pair)
-        multi = {mode: {"ms_per_step": elapsed / args.steps * 1e3, "pairs_per_step": pairs_per_step,
-                        "scaling": scaling, "primary": True}}
-        others = [x for x in ("dshard", "dshard_rep", "rowband", "pairdp") if x != mode]
-        del step
-        torch.cuda.empty_cache()
-        for om in others:
-            st2, pps2, sc2, _par2, res2 = make_mode(om, H, W, D, what, rank, world, args, Timer(), Timer(), Timer())
-            n2 = min(args.steps, 10)
-            el2 = timed_run(st2, n2, min(args.warmup, 3), None)
-            multi[om] = {"ms_per_step": el2 / n2 * 1e3, "pairs_per_step": pps2, "scaling": sc2,
-                         "Mvox_s": float(H) * W * D * pps2 * n2 / el2 / 1e6}
-            if args.dump_disp and rank == 0:
-                np.save(f"{args.dump_disp}.{om}.npy", res2().cpu().numpy())
-            del st2, res2
-            torch.cuda.empty_cache()
-    if args.dump_disp and rank == 0:
-        np.save(args.dump_disp, disp_primary.cpu().numpy())
-
+def full_report(args, m, what, mode, rank, world, H, W, D, t_conv, t_cv, t_tower, multi):
+    """--full: everything the result line carries beside the headline figure, each from runs of its own
+    after the timed steps -> (roofline, parity, host_io_ms, stages, cpu_baseline).  m: the pair-DP
+    matcher the timed steps ran (None for the sharded schemes); the timers hold the events of the
+    extra "conv" and "stages" steps; multi: the other multi-GPU schemes' times, or None."""
     vox = float(H) * W * D
-    value = vox * pairs_per_step * args.steps / elapsed / 1e6
-    ms_step = elapsed / args.steps * 1e3
-
+    left, right, _ = stereo_pair(H, W, D, seed=rank)     # this rank's pair (pair-DP; rank 0: seed 0)
     roof = None
     parity = None
     host_io_ms = None
@@ -787,6 +722,114 @@ def main():
                                   "whole host, whose other CPUs belong to other GPUs' jobs")
         if what in ("tower+cv_wta", "cv_wta"):
             cpu["numpy_restatement"] = numpy_baseline(H, W, D)
+    return roof, parity, host_io_ms, stages, cpu
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=50)     # ~0.1 s timed at the north star: 10 steps (20 ms) swung 2.05-2.25 ms/pair box to box
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--workload", default="north_star", choices=sorted(WORKLOADS))
+    ap.add_argument("--mode", default="auto", choices=["auto", "pairdp", "dshard", "dshard_rep", "rowband"])
+    ap.add_argument("--dump-disp", default=None, help="rank 0 saves the disparity map (.npy; auto mode with --full: "
+                                                         "also <path>.<mode>.npy for every other scheme)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline figure: stage and "
+                         "kernel times, roofline, parity checks, host I/O, the reference's GPU path, config 3, the "
+                         "other multi-GPU schemes and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-c3", action="store_true", help="--full, north_star: skip stages.c3 (BASELINE config 3 "
+                                                         "timed beside the line)")
+    ap.add_argument("--tower-precision", default="f16x3", choices=["fp32", "bf16x6", "f16x3", "f16x3w", "f16x3m32"])
+    ap.add_argument("--cv-mode", default="certified", choices=["certified", "exact"])
+    args = ap.parse_args()
+
+    rank, world, local = init_from_env()
+    if world != args.gpus and rank == 0:
+        print(f"warning: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
+    # (init_from_env selected the device: cuda:LOCAL_RANK, or LOCAL_RANK mod the device count for
+    # ranks sharing a GPU over gloo)
+    H, W, D, what = WORKLOADS[args.workload]
+    mode = resolve_mode(args.mode, world, what)
+
+    t_conv, t_cv, t_tower = Timer(), Timer(), Timer()
+    m = None
+    step, pairs_per_step, scaling, par, result = make_mode(mode, H, W, D, what, rank, world, args,
+                                                           t_conv, t_cv, t_tower)
+    if mode == "pairdp":
+        m = step.matcher
+
+    def timed_run(step_fn, nsteps, nwarm, timed):
+        for _ in range(nwarm):
+            step_fn()
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = None
+        for _ in range(nsteps):
+            out = step_fn(timed=timed)
+        torch.cuda.synchronize()
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        # max over ranks (gloo reduces host tensors: SDE_DIST_BACKEND=gloo runs ranks on a shared GPU)
+        tt = torch.tensor([el], dtype=torch.float64,
+                          device="cuda" if world == 1 or dist.get_backend() == "nccl" else "cpu")
+        if world > 1:
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        return float(tt.item()), out
+
+    elapsed, out = timed_run(step, args.steps, args.warmup, None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    del out
+    if args.full:
+        # layer 3's and the stages' times from extra steps outside the timed region (their events would
+        # add stream barriers to the timed steps)
+        for _ in range(args.steps):
+            step(timed="conv")
+        for _ in range(min(args.steps, 5)):
+            step(timed="stages")
+        torch.cuda.synchronize()
+    disp_primary = result().detach().clone() if args.dump_disp else None
+
+    multi = None
+    if args.full and world > 1 and args.mode == "auto" and what == "tower+cv_wta":
+        # the other multi-GPU schemes on the same pair, same ranks, same clock discipline (barrier +
+        # max over ranks); pair-DP is weak scaling (world pairs per step), the rest strong (one pair)
+        multi = {mode: {"ms_per_step": elapsed / args.steps * 1e3, "pairs_per_step": pairs_per_step,
+                        "scaling": scaling, "primary": True}}
+        others = [x for x in ("dshard", "dshard_rep", "rowband", "pairdp") if x != mode]
+        del step
+        torch.cuda.empty_cache()
+        for om in others:
+            st2, pps2, sc2, _par2, res2 = make_mode(om, H, W, D, what, rank, world, args, Timer(), Timer(), Timer())
+            n2 = min(args.steps, 10)
+            el2, _ = timed_run(st2, n2, min(args.warmup, 3), None)
+            multi[om] = {"ms_per_step": el2 / n2 * 1e3, "pairs_per_step": pps2, "scaling": sc2,
+                         "Mvox_s": float(H) * W * D * pps2 * n2 / el2 / 1e6}
+            if args.dump_disp and rank == 0:
+                np.save(f"{args.dump_disp}.{om}.npy", res2().cpu().numpy())
+            del st2, res2
+            torch.cuda.empty_cache()
+    if args.dump_disp and rank == 0:
+        np.save(args.dump_disp, disp_primary.cpu().numpy())
+
+    vox = float(H) * W * D
+    value = vox * pairs_per_step * args.steps / elapsed / 1e6
+    ms_step = elapsed / args.steps * 1e3
+
+    roof = parity = host_io_ms = cpu = None
+    stages = {}
+    if args.full:
+        roof, parity, host_io_ms, stages, cpu = full_report(args, m, what, mode, rank, world, H, W, D,
+                                                            t_conv, t_cv, t_tower, multi)
 
     if rank == 0:
         line = {

@@ -75,8 +75,8 @@ def test_bench_multirank_modes_on_one_gpu(gpu, tmp_path, mode, primary, scaling)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
            "--workload", "cones", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump-disp", dump]
-    if mode != "auto":
-        cmd += ["--mode", mode]
+    # the other schemes beside the auto line (stages.multi_gpu_modes and their maps) are a --full measurement
+    cmd += ["--mode", mode] if mode != "auto" else ["--full"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=110)
     if p.returncode != 0:
         print(p.stdout[-3000:], "\n---- stderr ----\n", "\n".join(l for l in p.stderr.splitlines() if "Gloo" not in l)[-6000:])
