@@ -1,0 +1,244 @@
+"""Adversarial inputs for the certified fused cost volume + WTA, and their analysis against the oracle.
+
+Shared by tests/test_cert_bound_model.py (CPU: the builder's own conditions, the model of the error
+bound) and tests/test_gpu_certificate.py (GPU: the kernels against the oracle on these inputs).
+
+near_tie_pair builds a stereo feature pair in which every left pixel has two disparities whose
+scores differ by 2 t, t from 0 to 2^-8, around the certificate's eps, optionally with single
+loud (or quiet) right pixels so that the window's largest norm matters.  analyse() measures, from
+the oracle's cost volume alone, how adversarial a built pair really is.
+"""
+import os
+import re
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "scenedepthestimation_amd", "csrc")
+SLACK = 64          # pixels of window slack per side: one 32-pixel tile + one 32-pixel group
+ROW_CHUNK = 256     # disparities per launch of the chunked row sweep (cost_volume.hip)
+
+
+def _const(text, name):
+    m = re.search(r"constexpr\s+(?:float|int)\s+" + name + r"\s*=\s*([-+0-9.eE]+)f?\s*;", text)
+    assert m, f"{name} not found in the kernel sources"
+    return float(m.group(1))
+
+
+def cert_constants():
+    """The certificate's constants as the kernels are built with them, read from the sources."""
+    with open(os.path.join(CSRC, "cv_row.hip")) as f:
+        row = f.read()
+    with open(os.path.join(CSRC, "cv_cert.h")) as f:
+        cert = f.read()
+    c = {n: _const(row, n) for n in ("RW_S", "RW_K", "RW_ABS", "RW_NMAX")}
+    c.update({n: _const(cert, n) for n in ("FX_K", "FX_ABS", "FX_NORM_UP")})
+    return c
+
+
+def l2n(x):
+    return (x / np.maximum(np.sqrt((x.astype(np.float64) ** 2).sum(-1, keepdims=True)), 1e-12)).astype(np.float32)
+
+
+T_GRID = np.array([0.0] + [2.0 ** -j for j in range(8, 25)])
+
+
+def near_tie_pair(rng, H, W, D, loud=None, scale=1.0, d0=0, loud_norm=None, loud_at=None):
+    """(fl, fr, info): fr unit-norm noise; every left pixel x > d0 gets two disparities d0 <= dA < dB <=
+    min(x, D - 1) with fl[x] . fr[x - dA] = c (1 - t) and fl[x] . fr[x - dB] = c (1 + t), fl[x] the
+    unit vector of span{a, b} that solves the 2 x 2 Gram system, t of random sign from T_GRID.
+
+    loud: exponents k; each row gets right pixels spaced D + 64 + randint(0, 32) apart from a random
+    start < 64, each multiplied by 2^k (k drawn from loud), so a left pixel's disparity range holds at
+    most one; where it holds one, that pixel is one of the two candidates.  (Only for factors above 1: a
+    unit fl[x] scores at most 2^k against a quiet pixel, below the ~0.36 that the best of the window's
+    other ~D unit pixels reaches, so for k <= -2 such a pair could never be the top two; the candidates
+    are then two ordinary pixels, and the quiet one only sits in the window.)  loud_norm: factors to draw
+    from instead of 2^k.  loud_at: the loud positions of each row, given (one list per row).
+    scale: power of two applied to both maps at the end."""
+    fr = l2n(rng.standard_normal((H, W, 64)).astype(np.float32))
+    fl = l2n(rng.standard_normal((H, W, 64)).astype(np.float32))
+    factors = None
+    if loud_norm is not None:
+        factors = [float(v) for v in loud_norm]
+    elif loud is not None:
+        factors = [2.0 ** k for k in loud]
+    loud_mask = np.zeros((H, W), bool)
+    forced = np.zeros((H, W), bool)     # loud pixels that must be one of the two candidates
+    if factors is not None:
+        for y in range(H):
+            if loud_at is not None:
+                qs = list(loud_at[y])
+            else:
+                qs, q = [], int(rng.integers(0, 64))
+                while q < W:
+                    qs.append(q)
+                    q += D + 64 + int(rng.integers(0, 32))
+            for q in qs:
+                f = factors[int(rng.integers(len(factors)))]
+                fr[y, q] *= np.float32(f)
+                loud_mask[y, q] = True
+                forced[y, q] = f > 1.0
+    dA = np.full((H, W), -1, np.int32)
+    dB = np.full((H, W), -1, np.int32)
+    tt = np.zeros((H, W))
+    fr64 = fr.astype(np.float64)
+    for y in range(H):
+        lq = np.flatnonzero(forced[y])
+        for x in range(d0 + 1, W):
+            hi = min(x, D - 1)
+            da, db = (int(v) for v in rng.choice(hi - d0 + 1, size=2, replace=False) + d0)
+            inr = lq[(lq >= x - hi) & (lq <= x - d0)]
+            if inr.size:
+                dq = x - int(inr[0])
+                if dq not in (da, db):
+                    if rng.integers(2):
+                        da = dq
+                    else:
+                        db = dq
+            da, db = min(da, db), max(da, db)
+            t = float(T_GRID[int(rng.integers(T_GRID.size))]) * (1.0 if rng.integers(2) else -1.0)
+            a, b = fr64[y, x - da], fr64[y, x - db]
+            G = np.array([[a @ a, a @ b], [a @ b, b @ b]])
+            c = np.linalg.solve(G, np.array([1.0 - t, 1.0 + t]))
+            v = c[0] * a + c[1] * b
+            fl[y, x] = (v / np.sqrt(v @ v)).astype(np.float32)
+            dA[y, x], dB[y, x], tt[y, x] = da, db, t
+    s = np.float32(scale)
+    fl *= s
+    fr *= s
+    info = {"dA": dA, "dB": dB, "t": tt, "built": dA >= 0, "loud": loud_mask, "scale": float(scale), "d0": d0, "D": D}
+    return fl, fr, info
+
+
+def window_max(v, lo, hi):
+    """out[y, x] = max(v[y, x - hi .. x - lo]) over the columns inside the image (0 where none is)."""
+    H, W = v.shape
+    out = np.zeros_like(v)
+    for s in range(lo, hi + 1):
+        if s >= 0:
+            if s < W:
+                out[:, s:] = np.maximum(out[:, s:], v[:, :W - s])
+        elif -s < W:
+            out[:, :W + s] = np.maximum(out[:, :W + s], v[:, -s:])
+    return out
+
+
+def analyse(cv, fl, fr, info, K, ABS, abs0=0.0):
+    """What the oracle's cost volume cv [D, H, W] says about a built pair, for eps = K nl wmax + ABS (nl + wmax) + abs0:
+
+    gap      the pixel's top-2 cost gap over [d0, D) (fp64 of the fp32 costs)
+    eps      with wmax over the pixel's own right window x - D + 1 .. x - d0
+    eps_unit the same with every loud pixel's norm replaced by the map's base norm: what a kernel that lost
+             the loud tile's maximum would use
+    eps_wide with the window widened by SLACK per side: at least what any kernel here uses (windows are
+             per 32-pixel group and 32-pixel tile, or per 64-pixel block)
+    exposed  some loud q with q - SLACK <= x <= q + D + SLACK
+    """
+    d0, D = info["d0"], info["D"]
+    H, W = fl.shape[:2]
+    c = np.sort(cv[d0:D].astype(np.float64), axis=0)
+    gap = c[1] - c[0] if D - d0 > 1 else np.full((H, W), np.inf)
+    nl = np.sqrt((fl.astype(np.float64) ** 2).sum(-1))
+    nr = np.sqrt((fr.astype(np.float64) ** 2).sum(-1))
+    nr_base = np.where(info["loud"], info["scale"], nr)
+
+    def eps_of(w):
+        return K * nl * w + ABS * (nl + w) + abs0
+    wmax = window_max(nr, d0, D - 1)
+    wwide = window_max(nr, d0 - SLACK, D - 1 + SLACK)
+    exposed = window_max(info["loud"].astype(np.float64), -SLACK, D + SLACK) > 0
+    return {"gap": gap, "nl": nl, "wmax": wmax, "wwide": wwide, "exposed": exposed,
+            "eps": eps_of(wmax), "eps_unit": eps_of(window_max(nr_base, d0, D - 1)), "eps_wide": eps_of(wwide)}
+
+
+def shares(an, info):
+    """The shares the tests assert on their own inputs."""
+    built = info["built"]
+    gap, eps = an["gap"], an["eps"]
+    band = (gap >= 0.25 * eps) & (gap <= 16 * eps)
+    wrong = (gap > 2 * an["eps_unit"]) & (gap <= 2 * eps)
+    ex = built & an["exposed"]
+    out = {"near": band[built].mean(), "ties": (gap[built] == 0).mean(),
+           "wrong_band": wrong[ex].mean() if ex.any() else 0.0, "exposed": ex.sum() / max(built.sum(), 1)}
+    b = info["d0"] + ROW_CHUNK
+    if info["D"] > b:
+        st = built & (info["dA"] < b) & (info["dB"] >= b)
+        out["straddle"] = st.sum() / built.sum()
+        out["straddle_signs"] = (bool((info["t"][st] > 0).any()), bool((info["t"][st] < 0).any()))
+    return out
+
+
+# ----------------------------------------------------------------------------
+# the cases: name -> (seed, D, d0, builder keywords, left_loud exponents or None)
+# ----------------------------------------------------------------------------
+H, W = 4, 1000
+UP, DOWN = (1, 2, 3, 4, 5, 6), (-6, -5, -4, -3, -2, -1)
+# tile edges, the 128-pixel superstrip edges, the first reuse of a ring slot (at D = 192 the ring holds 14
+# tiles from tile -6 on: tile 8 = pixel 256 is the first to land in a used slot), later tiles, the row's
+# ends; 63 / 64 fill the last launch
+SWEEP_Q = (0, 31, 32, 127, 128, 159, 160, 255, 256, 575, 576, 607, 608, W - 1, 63, 64)
+SCALES = (-40, -20, -12, 6, 7, 12)
+SCALE_INVARIANT = (-20, -12, 6, 7, 12)     # no exact cost under- or overflows: the map is the unscaled one
+
+CASES = {}
+for _i, (_D, _d0) in enumerate([(192, 0), (64, 0), (256, 17), (320, 0), (512, 0), (600, 5), (192, 40)]):
+    CASES[f"unit-D{_D}-d{_d0}"] = (10 + _i, _D, _d0, {}, None)
+for _i, _D in enumerate((192, 512)):
+    CASES[f"loud-up-D{_D}"] = (20 + _i, _D, 0, {"loud": UP}, None)
+    CASES[f"loud-64-D{_D}"] = (22 + _i, _D, 0, {"loud": (6,)}, None)
+    CASES[f"quiet-D{_D}"] = (24 + _i, _D, 0, {"loud": DOWN}, None)
+    CASES[f"left-loud-D{_D}"] = (26 + _i, _D, 0, {}, UP)
+for _i in range(len(SWEEP_Q) // H):
+    CASES[f"sweep-{_i}"] = (30 + _i, 192, 0, {"loud_norm": (64.0,), "loud_at": [[q] for q in SWEEP_Q[H * _i:H * _i + H]]},
+                            None)
+for _i, _n in enumerate((126.5, 127.5, 1e3, 1e4)):
+    CASES[f"guard-{_n:g}"] = (40 + _i, 192, 0, {"loud_norm": (_n,)}, None)
+for _e in SCALES:
+    CASES[f"scale-2^{_e}"] = (10, 192, 0, {"scale": 2.0 ** _e}, None)      # unit-D192-d0 scaled (same seed)
+
+# cases whose inputs must meet the adversarial shares below (the scaled maps share unit-D192-d0's pixels;
+# at a scale where RW_ABS dominates eps the band moves off the t grid)
+SHARE_CASES = [n for n in CASES if not n.startswith("scale-")]
+MIN_NEAR = 0.20        # built pixels with a top-2 gap in [0.25, 16] eps
+MIN_WRONG = 0.10       # exposed pixels with 2 eps(loud norm lost) < gap <= 2 eps, right pixels louder than the map
+MIN_STRADDLE = 0.10    # chunked: pixels with dA < d0 + 256 <= dB, both signs of t
+
+
+def build_case(name):
+    seed, D, d0, kw, left = CASES[name]
+    rng = np.random.default_rng(seed)
+    fl, fr, info = near_tie_pair(rng, H, W, D, d0=d0, **kw)
+    if left is not None:
+        # the loud pixels on the left instead: rows of fl scaled after building (scores and gaps of
+        # those pixels scale with them, as their eps does)
+        for y in range(H):
+            q = int(rng.integers(0, 64))
+            while q < W:
+                fl[y, q] *= np.float32(2.0 ** left[int(rng.integers(len(left)))])
+                q += 32 + int(rng.integers(0, 64))
+    return fl, fr, info
+
+
+def raises_window_norm(name):
+    """The case has right pixels louder than the rest of the map (the wrongly-certifiable band exists)."""
+    kw = CASES[name][3]
+    return any(k > 0 for k in kw.get("loud", ())) or any(v > 1 for v in kw.get("loud_norm", ()))
+
+
+def check_shares(name, sh):
+    """The conditions a case's inputs must meet, from the oracle's volume (shares() of analyse())."""
+    # (loud norms past the fp16 range guard: no eps certifies the exposed pixels, and eps at norm 1e3 lies
+    # above the t grid; what those cases need is the band below, pixels that ignoring the loud tile would certify)
+    if max(CASES[name][3].get("loud_norm", (0,))) < 1e3:
+        assert sh["near"] >= MIN_NEAR, (name, sh)
+    assert sh["ties"] > 0, (name, sh)
+    if raises_window_norm(name) and not name.startswith("sweep-"):
+        assert sh["wrong_band"] >= MIN_WRONG, (name, sh)
+    if "straddle" in sh:
+        assert sh["straddle"] >= MIN_STRADDLE and sh["straddle_signs"] == (True, True), (name, sh)
+
+
+def single_sweep(d0, d1):
+    """cv_row.hip's row2_supported: the range fits one row sweep's ring (else 256-disparity chunks)."""
+    return (127 - d0) // 32 - (-(d1 - 1)) // 32 + 1 <= 14
