@@ -81,10 +81,8 @@ __global__ __launch_bounds__(256) void cbca_transpose_kernel(const uint32_t *__r
 }
 
 // Cache policy of the cost streams (aux bit 1 = nt on gfx950): each voxel is read once and written
-// once per pass (round 2: nontemporal both ways, 1.513 -> 1.468 ms per pair iteration).
-#ifndef CBCA_NT
-#define CBCA_NT 3
-#endif
+// once per pass, so both ways are nontemporal (round 2: 1.513 -> 1.468 ms per pair iteration).
+constexpr int CB_NT = 2;
 constexpr uint32_t CB_OOB = 0x80000000u;    // a voffset past every range: load 0, store dropped
 
 // Buffer descriptor (wave-uniform inputs only) for raw dword loads/stores with a 32-bit per-lane
@@ -125,15 +123,9 @@ __device__ __forceinline__ double cb_recip(uint32_t c)
     return __builtin_fma(r, e, r);
 }
 
-// Chain arithmetic: fp64 (definition v2).  CBCA_P32 builds (timing probes, tools/build_file_variant.sh) run the
-// chains, rings and the mean's reciprocal in fp32 -- different results, half the ring LDS.
-#ifdef CBCA_P32
-typedef float cb_p;
-typedef float cb_r;
-#else
+// Chain arithmetic: fp64 (definition v2) for the chains and rings (cb_p) and the mean's reciprocal (cb_r).
 typedef double cb_p;
 typedef double cb_r;
-#endif
 
 struct CbcaArgs {
     const float *src;
@@ -206,7 +198,7 @@ __device__ __forceinline__ void cbca_h_item(const CbcaArgs &A, int y, int c, int
 #pragma unroll
     for (int j = 0; j < PF; j++)
         cr[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, dl4, (int)(D4 * (uint32_t)min(fs + j, W - 1)),
-                                                                               CBCA_NT & 1 ? 2 : 0));
+                                                                               CB_NT));
     cb_p P = 0.0;
     sP[(RS - 1) * 64 + lane] = 0.0;               // P(fs - 1) = 0: read before position fs + RS - 1 lands
     // per-lane store offset of output t (4d + 4tD), advanced every step
@@ -230,12 +222,12 @@ __device__ __forceinline__ void cbca_h_item(const CbcaArgs &A, int y, int c, int
         P += (!SEL || f >= d) ? (cb_p)cv : (cb_p)0.0;
         sP[j * 64 + lane] = P;
         const uint32_t so = clamp ? D4 * (uint32_t)min(f + PF, W - 1) : sld;
-        cr[slot] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, dl4, (int)so, CBCA_NT & 1 ? 2 : 0));
+        cr[slot] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, dl4, (int)so, CB_NT));
         sld = opq_s(sld + D4);
         __builtin_amdgcn_sched_barrier(0);
         const float out = (float)(pb - pa);
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, out), rd, t >= th ? vst : CB_OOB, 0,
-                                              CBCA_NT & 2 ? 2 : 0);
+                                              CB_NT);
         vst = opq_v(vst + D4);
     };
     // Blocks of RS steps.  The block arms alternate between two register pairs, each reloaded in
@@ -355,7 +347,7 @@ __device__ __forceinline__ void cbca_v_item(const CbcaArgs &A, int x, int c, int
 #pragma unroll
         for (int j = 0; j < PF; j++)
             cr[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                  rc0, dl4, (int)(rowv * (uint32_t)(min(fs + j, H - 1) - fs)), CBCA_NT & 1 ? 2 : 0));
+                                                  rc0, dl4, (int)(rowv * (uint32_t)(min(fs + j, H - 1) - fs)), CB_NT));
     }
 #pragma unroll
     for (int j = 0; j < U; j++) sup[j] = 0u;
@@ -409,7 +401,7 @@ __device__ __forceinline__ void cbca_v_item(const CbcaArgs &A, int x, int c, int
         sup[j % U] = (m02 >> 16) | (m13 & 0xFFFF0000u);
         Bq[j] = arm_r(f + RS);                              // the next block's row
         const uint32_t so = clamp ? rowv * (uint32_t)(min(f + PF, H - 1) - fbase) : sld;
-        cr[slot] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, dl4, (int)so, CBCA_NT & 1 ? 2 : 0));
+        cr[slot] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc, dl4, (int)so, CB_NT));
         sld = opq_s(sld + rowv);
         __builtin_amdgcn_sched_barrier(0);
         // the output (row t = f - R - 1: soffset j rows on the block's store descriptor)
@@ -419,7 +411,7 @@ __device__ __forceinline__ void cbca_v_item(const CbcaArgs &A, int x, int c, int
         const cb_r rcp = CbV<R>::TAB ? tab[min(cnt, (uint32_t)CbV<R>::NT - 1)] : (cb_r)cb_recip(cnt);
         const float out = (float)(num * rcp);
         const uint32_t vo = (lane_ok && t >= t0) ? 4u * (uint32_t)d : CB_OOB;
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, out), rd, vo, (int)sst, CBCA_NT & 2 ? 2 : 0);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, out), rd, vo, (int)sst, CB_NT);
         sst = opq_s(sst + rowv);
     };
     int fb = fs;
@@ -560,7 +552,7 @@ __global__ __launch_bounds__(256) void cbca_rotate_kernel(const float *__restric
             uint32_t vraw = 4u * ((uint32_t)q * D + d);
             asm volatile("" : "+v"(vraw));
             v[b] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                 ri, ok_m >= 0 ? vraw : CB_OOB, 0, CBCA_NT & 1 ? 2 : 0));
+                                                 ri, ok_m >= 0 ? vraw : CB_OOB, 0, CB_NT));
             at[b] = in_m >= 0 ? p * RT_ND + e : RT_NP * RT_ND + lane;
         }
 #pragma unroll
@@ -582,7 +574,7 @@ __global__ __launch_bounds__(256) void cbca_rotate_kernel(const float *__restric
         }
 #pragma unroll
         for (int b = 0; b < WB; b++)
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[b]), ro, vo[b], 0, CBCA_NT & 2 ? 2 : 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v[b]), ro, vo[b], 0, CB_NT);
     }
 }
 

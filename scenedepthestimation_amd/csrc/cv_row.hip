@@ -328,15 +328,10 @@ __global__ __launch_bounds__(512) void cv_wta_row_kernel(const float *__restrict
 // superstrip k-1 retired (ring = window + 4 tiles: 14 at D = 192, 112 KB).
 // ---------------------------------------------------------------------------
 constexpr int R2_NX = 128;                 // left pixels per superstrip (4 compute waves x 32)
-#ifndef CV_FASTSPLIT
-#define CV_FASTSPLIT 63                    // bits: 1 paired split, 2 norm-based flag, 4 swap merges, 8 norm total by shuffle,
-                                           // 16 the stagers' flag from the pixel norm, 32 the stagers' paired split
-                                           // (A/B builds)
-#endif
 constexpr int R2_NEW = R2_NX / RW_T;       // tiles admitted per superstrip (4)
-#ifndef CV_LEAD
-#define CV_LEAD 2                          // scores issued before the next tile's first MFMA (A/B builds: 2..8)
-#endif
+constexpr int R2_LEAD = 2;                 // scores issued before the next tile's first MFMA (2..8 measured)
+// (the paired splits, the norm-based non-finite flags and the merge by permlane32 swaps below were each measured
+// against the plain form in round 5, DESIGN "Round 5 status")
 
 // one stager lane's 8 units (pixel u >> 4, channels 4 (u & 15) ..) of right tile T: unit u = lane + 64 i
 __device__ __forceinline__ void r2_load(const float *__restrict__ frrow, int W, int T, int lane, float4 (&v)[8])
@@ -355,7 +350,6 @@ __device__ __forceinline__ void r2_store(uint4 *ring, unsigned *tmax, unsigned *
     for (int i = 0; i < 8; i++) {
         const int u = lane + 64 * i, px = u >> 4, q = u & 15;
         char *base = reinterpret_cast<char *>(ring + slot * 512 + fx_slot(px, q >> 1)) + 8 * (q & 1);
-#if CV_FASTSPLIT & 32
         // rw_split's parts as the compute waves' left split: hi of a scaled pair by one packed convert, lo by
         // v_fma_mix{lo,hi} from it (x 2^S - hi exact in fp32: the same bits)
         const float xs[4] = {v[i].x * RW_SCALE, v[i].y * RW_SCALE, v[i].z * RW_SCALE, v[i].w * RW_SCALE};
@@ -370,14 +364,6 @@ __device__ __forceinline__ void r2_store(uint4 *ring, unsigned *tmax, unsigned *
         }
         *reinterpret_cast<uint2 *>(base) = uint2{hw[0], hw[1]};
         *reinterpret_cast<uint2 *>(base + 256 * 16) = uint2{lw[0], lw[1]};
-#else
-        _Float16 h0, h1, h2, h3, l0, l1, l2, l3;
-        rw_split(v[i].x, h0, l0); rw_split(v[i].y, h1, l1); rw_split(v[i].z, h2, l2); rw_split(v[i].w, h3, l3);
-        typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-        const h4 hv = {h0, h1, h2, h3}, lv = {l0, l1, l2, l3};
-        *reinterpret_cast<uint2 *>(base) = __builtin_bit_cast(uint2, hv);
-        *reinterpret_cast<uint2 *>(base + 256 * 16) = __builtin_bit_cast(uint2, lv);
-#endif
         // the pixel's squared norm: its 16 lanes are one DPP row (same adds as rw_store)
         float ss = v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
         ss += rw_dpp<0xB1>(ss);
@@ -385,13 +371,9 @@ __device__ __forceinline__ void r2_store(uint4 *ring, unsigned *tmax, unsigned *
         ss += rw_dpp<0x141>(ss);
         ss += rw_dpp<0x140>(ss);
         mx = max(mx, __float_as_uint(ss));          // non-negative: bit patterns order as unsigned
-#if CV_FASTSPLIT & 16
         // a non-finite channel makes the pixel's sum of squares non-finite: one test per pixel (the norm
         // bound then fails the certificate as well: NaN / inf bits order above every finite square)
         bad |= rw_nonfinite(ss);
-#else
-        bad |= rw_nonfinite(v[i].x) || rw_nonfinite(v[i].y) || rw_nonfinite(v[i].z) || rw_nonfinite(v[i].w);
-#endif
     }
     // whole-wave maximum (every lane holds its rows' pixel norms) and any-non-finite
 #pragma unroll
@@ -491,7 +473,6 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
         } else if (xb < W) {   // wave-uniform
             rw_f16x8 bh[4], bl[4];
             float ssl = 0.0f;
-#if CV_FASTSPLIT & 1
             // rw_split's parts two values at a time: hi by one packed convert of the scaled pair, lo =
             // f16(x 2^S - hi) by v_fma_mix{lo,hi} (x 2^S exact, x 2^S - hi exact in fp32: the same bits)
             const float scl = RW_SCALE;
@@ -517,39 +498,13 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                 bh[s2] = __builtin_bit_cast(rw_f16x8, uint4{hw[0], hw[1], hw[2], hw[3]});
                 bl[s2] = __builtin_bit_cast(rw_f16x8, uint4{lw[0], lw[1], lw[2], lw[3]});
             }
-#else
-#pragma unroll
-            for (int s2 = 0; s2 < 4; s2++) {
-                const float4 a = lraw[2 * s2], b = lraw[2 * s2 + 1];
-                const float v8[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    _Float16 hh, ll;
-                    rw_split(v8[e], hh, ll);
-                    bh[s2][e] = hh;
-                    bl[s2][e] = ll;
-                    ssl += v8[e] * v8[e];
-                    if (!(CV_FASTSPLIT & 2)) lbad |= rw_nonfinite(v8[e]);
-                }
-            }
-#endif
-#if CV_FASTSPLIT & 2
             // a non-finite channel makes the sum of squares non-finite (an overflowing sum of finite squares
             // is flagged too: that pixel goes to the exact fix-up, same outputs).  The other half's partial
-            // sum by the LDS shuffle (bit 8): with a permlane32 swap here the build's fix-up counts moved
+            // sum by the LDS shuffle: with a permlane32 swap here the build's fix-up counts moved
             // (693 -> 709 at 512 x 2048, same maps) -- the swap's result in lanes 0-31 was not the other
             // half's sum in that schedule, so the norm bound would be wrong; not used
-#if CV_FASTSPLIT & 8
             ssl += __shfl_xor(ssl, 32, 64);
-#else
-            ssl += __builtin_bit_cast(float, __builtin_amdgcn_permlane32_swap(__float_as_uint(ssl), __float_as_uint(ssl),
-                                                                              false, false)[1]);
-#endif
             lbad = rw_nonfinite(ssl);
-#else
-            ssl += __shfl_xor(ssl, 32, 64);
-            lbad |= __shfl_xor((int)lbad, 32, 64) != 0;
-#endif
             nl = sqrtf(ssl) * FX_NORM_UP;
             if (more) load_left(k + 1);
 
@@ -624,9 +579,9 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                     int dk[4];
 #pragma unroll
                     for (int k2 = 0; k2 < 4; k2++) dk[k2] = dl - 8 * k2;
-                    // CV_LEAD scores before the next tile's first MFMA (they cover its fragments' LDS reads), the
-                    // other 16 - CV_LEAD spread over the 12 MFMA gaps
-                    constexpr int LD = CV_LEAD, RS = 16 - CV_LEAD;
+                    // R2_LEAD scores before the next tile's first MFMA (they cover its fragments' LDS reads), the
+                    // other 16 - R2_LEAD spread over the 12 MFMA gaps
+                    constexpr int LD = R2_LEAD, RS = 16 - R2_LEAD;
                     auto body = [&](auto mode_c) {
 #pragma unroll
                         for (int r = 0; r < LD; r++) score1(acc, r, mode_c, dk);
@@ -686,15 +641,10 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
 #pragma unroll
             for (int t = 1; t < 4; t++) fx_merge(best, arg, second, b1[t], ag[t], b2[t]);
             {
-#if CV_FASTSPLIT & 4
                 // lanes 0-31 (the ones that store) take the other half's triple by permlane32 swaps
                 auto up = [](uint32_t v) { return __builtin_amdgcn_permlane32_swap(v, v, false, false)[1]; };
                 const float bb = __uint_as_float(up(__float_as_uint(best))), ss2 = __uint_as_float(up(__float_as_uint(second)));
                 const int aa = (int)up((uint32_t)arg);
-#else
-                const float bb = __shfl_xor(best, 32, 64), ss2 = __shfl_xor(second, 32, 64);
-                const int aa = __shfl_xor(arg, 32, 64);
-#endif
                 fx_merge(best, arg, second, bb, aa, ss2);
             }
             if constexpr (WANT_MIN) {

@@ -47,6 +47,19 @@ static inline bool once_per_device(std::atomic<uint64_t> &done, F fn)
     return ok;
 }
 
+// Launch kernel K with SMEM bytes of dynamic LDS.  More than 64 KB needs a per-device opt-in on the kernel:
+// it is made here, on K's first launch on a device, so no instantiation can be launched without it.  (The
+// function-local atomic is trivially destructible: no exit-time code.)
+template <auto K, size_t SMEM, typename... Args>
+static inline void launch_lds(dim3 grid, dim3 block, hipStream_t st, Args... args)
+{
+    static std::atomic<uint64_t> done{0};
+    once_per_device(done, [] {
+        (void)hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM);
+    });
+    hipLaunchKernelGGL(K, grid, block, SMEM, st, args...);
+}
+
 // 64-float (256 B) rows in LDS, XOR-swizzled at 16-B granularity: the 16 lanes
 // of one ds_read_b128 group that read the same logical chunk of 16 consecutive
 // rows land on 16 distinct 16-B slots of the 256-B bank row (conflict-free).

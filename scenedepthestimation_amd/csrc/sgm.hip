@@ -27,17 +27,11 @@
 // right image sides (the reference's k loop) run in the same launch (grid.y).
 #include "sde_common.h"
 
-// The cost and S streams are touched once per pass: nontemporal loads and stores (1 | 2).  Both
-// together: 6.44 -> 5.96 ms for the 7-launch pair (either alone: no change; tools/sgm_variants.py).
-#ifndef SGM_NT
-#define SGM_NT 3
-#endif
-// Fused WTA bookkeeping: 1 parks each step's S values in LDS and scans a pixel's D values in d
-// order spread over the next block's steps (no per-step lane-local argmin, no index tie-breaks
-// until the G-lane DPP merge); 0 the round-3 lane-partial form (A/B builds).
-#ifndef SGM_WTA_PARK
-#define SGM_WTA_PARK 1
-#endif
+// The cost and S streams are touched once per pass: nontemporal loads and stores.  Both together:
+// 6.44 -> 5.96 ms for the 7-launch pair (either alone measured no change).
+// Fused WTA bookkeeping: each step's S values are parked in LDS and a pixel's D values are scanned
+// in d order spread over the next block's steps (no per-step lane-local argmin, no index tie-breaks
+// until the G-lane DPP merge); the round-3 lane-partial form it replaced measured slower.
 
 namespace sde {
 
@@ -73,11 +67,6 @@ __device__ __forceinline__ void path_pixel(const PathGeom &g, int line, int k, i
         }
     }
 }
-
-template <int N>
-struct alignas(4) FVec {
-    float v[N];
-};
 
 // DPP move of a double (two 32-bit halves); lanes outside ROW_MASK keep `v`.
 template <int CTRL, int ROW_MASK = 0xF>
@@ -395,73 +384,53 @@ template <int DPL>
 struct Slot {
     typename SgmV<DPL>::T c;
     typename SgmV<DPL>::T s;
-    float p1, p2;   // p1 as loaded: the step applies `pin` (a select at issue would wait for the load);
-                    // SGM_WALK: this pixel's P1 channel, the NEXT step's P1
+    float p1, p2;   // this pixel's P1 channel (the NEXT step's P1) and P2
     size_t off;     // voxel offset of (r, c, d = 0)
     int pix;        // pixel index r W + c (the fused WTA's output index; no 64-bit division by D per step)
     bool restart;
-    bool pin;       // the previous pixel is inside the image (else P1 = 0); unused under SGM_WALK
 };
 
 // Incremental walk along a scanline (wave-uniform scalars; no divisions).  Same
 // pixel sequence as path_pixel: diagonal lines wrap around the image with a
 // path restart.  Steps past the end of the line are clamped into the image (the
 // kernel re-reads valid memory there and stores nothing).
-// SGM_WALK (the default): the pixel index itself advances (one 64-bit scalar add per step, and a
+// The pixel index itself advances (one 64-bit scalar add per step, and a
 // +-W on a diagonal wrap) and stops at the line's last pixel, instead of clamping (r, c) and
 // recomputing r W + c and the previous pixel's index with 64-bit multiplies on every step.  A
 // step's predecessor on the path is the previous step's pixel unless the step restarts the path
 // (line start, diagonal wrap), which is exactly when the reference's P1 pixel is outside the
 // image -- so P1 is carried from the previous step and one 8-byte load per step fetches (P1, P2)
 // of the pixel (channels ch, ch + 1; ch even).
-#ifndef SGM_WALK
-#define SGM_WALK 1
-#endif
-#ifndef SGM_EDGESEL
-#define SGM_EDGESEL 1  // D = 64 DPL kernels: the edge lanes' missing neighbours by selects, not branches
-#endif
 struct Walker {
-    int r, c;
+    int r, c;           // r: the line's first row (init only; as a local it swaps a multiply's operands)
     bool restart;
-    int left;           // SGM_WALK: moves left before the line's last pixel
-    long long dpx;      // SGM_WALK: pixel-index step dr W + dc
-    size_t px;          // SGM_WALK: the pixel index r W + c
+    int left;           // moves left before the line's last pixel
+    long long dpx;      // pixel-index step dr W + dc
+    size_t px;          // the pixel index r W + c
     __device__ __forceinline__ void init(const PathGeom &g, int line)
     {
         if (g.dc == 0) { c = line; r = g.dr > 0 ? 0 : g.H - 1; }
         else if (g.dr == 0) { r = line; c = g.dc > 0 ? 0 : g.W - 1; }
         else { r = g.dr > 0 ? 0 : g.H - 1; c = line; }
         restart = true;
-        if (SGM_WALK) {
-            const int nlen = (g.dc != 0 && g.dr == 0) ? g.W : g.H;
-            left = min(g.n, nlen) - 1;
-            dpx = (long long)g.dr * g.W + g.dc;
-            px = (size_t)r * g.W + c;
-        }
+        const int nlen = (g.dc != 0 && g.dr == 0) ? g.W : g.H;
+        left = min(g.n, nlen) - 1;
+        dpx = (long long)g.dr * g.W + g.dc;
+        px = (size_t)r * g.W + c;
     }
     __device__ __forceinline__ void advance(const PathGeom &g)
     {
-        if (SGM_WALK) {
-            // selects, not branches (scalar s_cselect; the step is one basic block)
-            const bool mv = left > 0;
-            left -= mv ? 1 : 0;
-            c += mv ? g.dc : 0;
-            px += mv ? dpx : 0;
-            restart = false;
-            if (g.dr != 0 && g.dc != 0) {
-                const bool wr = g.dc > 0 ? c >= g.W : c < 0;
-                c = wr ? (g.dc > 0 ? 0 : g.W - 1) : c;
-                px = wr ? (g.dc > 0 ? px - g.W : px + g.W) : px;
-                restart = wr;
-            }
-            return;
-        }
-        r += g.dr;
-        c += g.dc;
+        // selects, not branches (scalar s_cselect; the step is one basic block)
+        const bool mv = left > 0;
+        left -= mv ? 1 : 0;
+        c += mv ? g.dc : 0;
+        px += mv ? dpx : 0;
         restart = false;
         if (g.dr != 0 && g.dc != 0) {
-            if (c >= g.W) { c = 0; restart = true; }
-            else if (c < 0) { c = g.W - 1; restart = true; }
+            const bool wr = g.dc > 0 ? c >= g.W : c < 0;
+            c = wr ? (g.dc > 0 ? 0 : g.W - 1) : c;
+            px = wr ? (g.dc > 0 ? px - g.W : px + g.W) : px;
+            restart = wr;
         }
     }
 };
@@ -472,48 +441,23 @@ template <int DPL, bool VEC, bool FIRST>
 __device__ __forceinline__ void issue(const PathGeom &g, const Walker &w, const SgmSide &sd, int D, int dbase,
                                       Slot<DPL> &sl)
 {
-    size_t px;
-    if (SGM_WALK) {
-        px = w.px;
-        const float2 pp = *reinterpret_cast<const float2 *>(sd.pen + px * 16 + g.ch);
-        sl.p1 = pp.x;
-        sl.p2 = pp.y;
-    } else {
-        const int r = min(max(w.r, 0), g.H - 1), c = min(max(w.c, 0), g.W - 1);
-        px = (size_t)r * g.W + c;
-        int pr = r - g.dr, pc = c - g.dc;
-        const bool pin = pr >= 0 && pr < g.H && pc >= 0 && pc < g.W;
-        pr = pin ? pr : r;
-        pc = pin ? pc : c;
-        sl.p1 = sd.pen[((size_t)pr * g.W + pc) * 16 + g.ch];
-        sl.pin = pin;
-        sl.p2 = sd.pen[px * 16 + g.ch + 1];
-    }
+    const size_t px = w.px;
+    const float2 pp = *reinterpret_cast<const float2 *>(sd.pen + px * 16 + g.ch);
+    sl.p1 = pp.x;
+    sl.p2 = pp.y;
     sl.restart = w.restart;
     sl.pix = (int)px;
     const size_t off = px * D;
     sl.off = off;
     if (VEC) {
-        const size_t o = off + (dbase < D ? dbase : 0);
-        if (SGM_NT & 1) {
-            // wave-uniform row pointers + a 32-bit lane offset: the loads take the SGPR-base form
-            const float *cvp = sd.cv + off, *sp = sd.S + off;
-            const unsigned lo = (unsigned)(dbase < D ? dbase : 0);
+        // wave-uniform row pointers + a 32-bit lane offset: the loads take the SGPR-base form
+        const float *cvp = sd.cv + off, *sp = sd.S + off;
+        const unsigned lo = (unsigned)(dbase < D ? dbase : 0);
 #pragma unroll
-            for (int i = 0; i < DPL; i++) sl.c[i] = __builtin_nontemporal_load(cvp + lo + i);
-            if (!FIRST)
+        for (int i = 0; i < DPL; i++) sl.c[i] = __builtin_nontemporal_load(cvp + lo + i);
+        if (!FIRST)
 #pragma unroll
-                for (int i = 0; i < DPL; i++) sl.s[i] = __builtin_nontemporal_load(sp + lo + i);
-        } else {
-        const FVec<DPL> cv = *reinterpret_cast<const FVec<DPL> *>(sd.cv + o);
-#pragma unroll
-        for (int i = 0; i < DPL; i++) sl.c[i] = cv.v[i];
-        if (!FIRST) {
-            const FVec<DPL> sv = *reinterpret_cast<const FVec<DPL> *>(sd.S + o);
-#pragma unroll
-            for (int i = 0; i < DPL; i++) sl.s[i] = sv.v[i];
-        }
-        }
+            for (int i = 0; i < DPL; i++) sl.s[i] = __builtin_nontemporal_load(sp + lo + i);
     } else {
 #pragma unroll
         for (int i = 0; i < DPL; i++) {
@@ -557,21 +501,14 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
     const int lane = threadIdx.x & 63;      // one wave per block: lane < 64 known to the compiler
     const int dbase = lane * DPL;
     const double INF = __builtin_inf();
-    // fused WTA: per-step lane partials of the last PF steps (wave-private: one wave per block).
-    // G = 64 / PF lanes merge one step; lane l's partial of step j sits at j * WS + (l % PF) * G +
-    // l / PF with WS = 64 + G: the merge's reads (lane (st, q) takes partials q, q + G, .. of step
-    // st) then hit 32 distinct banks per half-wave -- the straight j * 64 + l layout made the merge
-    // reads 8-way conflicted (PMC: 65 % of the launch's LDS cycles were conflicts).  Within a step's
-    // row, the G-word group of lane l % PF is XOR-swizzled by (l % PF) & 4: lanes l and l + 4 (same
-    // l / PF, rows 32 words apart in bank space) then land in disjoint halves of their 8 banks, so
-    // the per-step ds_write_b32s are conflict-free too (were 2-way: 28 % of the launch's LDS cycles)
-    // The merge of a block of PF steps is spread over the next block's steps (one partial read and
-    // merge per step, the G-lane DPP reduction and the store at its last step), so the loop body
-    // stays one uniform step: a separate merge block after every PF steps made the compiler rotate
-    // the prefetch ring's registers at the loop back-edge and drain it (vmcnt(0) every PF steps).
-    // Partials and pixel indices are double-buffered by block parity.
+    // fused WTA: the S values of the last PF steps (wave-private: one wave per block); G = 64 / PF
+    // lanes scan one step's pixel.  The scan of a block of PF steps is spread over the next block's
+    // steps (one read and compare per step, the G-lane DPP reduction and the store at its last step),
+    // so the loop body stays one uniform step: a separate merge block after every PF steps made the
+    // compiler rotate the prefetch ring's registers at the loop back-edge and drain it (vmcnt(0)
+    // every PF steps).  Values and pixel indices are double-buffered by block parity.
     //
-    // SGM_WTA_PARK (the default): each step parks its 64 DPL S values (+inf past D), value i of lane
+    // Each step parks its 64 DPL S values (+inf past D), value i of lane
     // l at word i IS + l of a row of RS words, and lane (st, q) scans pixel st's disparities
     // DPL (PF q + j) + i, i < DPL, at step j of the next block -- the values lane PF q + j parked --
     // in increasing d with a strict `<` (the reference's sequential scan over its chunk), so only the
@@ -581,10 +518,8 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
     // conflict-free (a [lane][i] row with stride DPL had the pair's words collide: 12.6 M conflict
     // cycles per pair of launches).
     constexpr int IS = 68, RS = ((DPL * IS + 63) / 64) * 64 + 1;
-    constexpr int G = 64 / PF, WS = 64 + G;
-    constexpr bool PARK = SGM_WTA_PARK != 0;
-    __shared__ float wbv[WTA ? 2 * PF * (PARK ? RS : WS) : 1];
-    __shared__ int wba[WTA && !PARK ? 2 * PF * WS : 1];
+    constexpr int G = 64 / PF;
+    __shared__ float wbv[WTA ? 2 * PF * RS : 1];
     __shared__ int wpx[WTA ? 2 * PF : 1];
     __shared__ FaithLds<DPL> flds;
 
@@ -631,7 +566,7 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
 
     double L[DPL];
     double m = 1.0, mP2 = 1.0;
-    float p1c = 0.0f;              // SGM_WALK: the previous step's pixel's P1 channel
+    float p1c = 0.0f;              // the previous step's pixel's P1 channel
     int kf = -1;                   // first step with a non-finite cost: the line continues faithfully
     bool redo = false;             // DU fold (FIRST): recompute the column in the faithful arithmetic
 #pragma unroll
@@ -648,14 +583,14 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
         for (int j = 0; j < PF; j++) {
             const int k = k0 + j;     // steps k >= n compute on a clamped pixel and store nothing
             const Slot<DPL> &sl = ring[j];
-            const float p1f = SGM_WALK ? (sl.restart ? 0.0f : p1c) : (sl.pin ? sl.p1 : 0.0f);
+            const float p1f = sl.restart ? 0.0f : p1c;
             // (wave-uniform; into an SGPR for the reason given for p1c below)
             const float p2f = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sl.p2)));
             // read before the slot's refill at the end of this step, into an SGPR: carried as the
             // slot's own VGPR it stayed live across the refill, so the refill took other registers and
             // the loop latch copied every slot's penalty pair back -- waiting for each load in turn,
             // which drained the prefetch ring once per PF steps
-            if (SGM_WALK) p1c = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sl.p1)));
+            p1c = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sl.p1)));
             if (DU) {
                 if (FIRST && !redo) redo = any_nonfinite_v<DPL>(sl.c, p1f, p2f);
             } else if (kf < 0 && k < g.n && any_nonfinite_v<DPL>(sl.c, p1f, p2f)) {
@@ -678,7 +613,7 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
                     double b = L[i];
                     const double left = i > 0 ? L[i - 1] : lo;
                     const double right = i < DPL - 1 ? L[i + 1] : hi;
-                    if (DC && SGM_EDGESEL) {
+                    if (DC) {
                         // D = 64 DPL: only lane 0's first and lane 63's last disparity lack a
                         // neighbour -- a select of +inf (min(b, inf) = b) instead of an exec-masked
                         // branch per step
@@ -704,7 +639,7 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
                     o[i] = (float)((double)o[i] + (du_first ? c : c + 0.0));
                 }
             }
-            if (WTA && PARK) {
+            if (WTA) {
                 // this step's S values parked; one piece of the previous block's scan (below), off
                 // the recurrence's serial chain
                 float *row = wbv + (buf * PF + j) * RS + lane;
@@ -730,28 +665,6 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
                     }
                     if (j == PF - 1) wta_block_store<G>(mv_b, mv_a, wpx[(buf ^ 1) * PF + wst], wq, sd.disp);
                 }
-            } else if (WTA) {
-                // lane-local first-min over this lane's disparities, parked in LDS; the 64-way
-                // merge runs once per PF steps (below), off the recurrence's serial chain
-                float bv = __builtin_inff();
-                int ba = 0x7fffffff;
-#pragma unroll
-                for (int i = 0; i < DPL; i++)
-                    if (dbase + i < D && o[i] < bv) { bv = o[i]; ba = dbase + i; }
-                if (lane == 0 && o[0] != o[0]) { bv = -__builtin_inff(); ba = 0; }   // NaN S(0): d = 0
-                const int slot = (buf * PF + j) * WS + (lane % PF) * G + ((lane / PF) ^ (lane % PF & 4));
-                wbv[slot] = bv;
-                wba[slot] = ba;
-                if (lane == 0) wpx[buf * PF + j] = (k < g.n && keep) ? sl.pix : -1;
-                // one step of the previous block's merge (nothing to merge in the first block)
-                if (k0 > 0) {
-                    const int rs = ((buf ^ 1) * PF + wst) * WS + j * G + (wq ^ (j & 4));
-                    const float v2 = wbv[rs];
-                    const int a2 = wba[rs];
-                    if (j == 0) { mv_b = v2; mv_a = a2; }
-                    else wta_merge(mv_b, mv_a, v2, a2);
-                    if (j == PF - 1) wta_block_store<G>(mv_b, mv_a, wpx[(buf ^ 1) * PF + wst], wq, sd.disp);
-                }
             } else if (VEC) {
                 // every step stores: a step that must not (past the line's end, a line gone faithful)
                 // writes the dump row instead.  A store behind a branch left the waitcnt pass unsure
@@ -759,16 +672,9 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
                 // instead of PF: the prefetch ring was mostly idle.
                 float *const sbase = (k < g.n && keep) ? sd.S + sl.off : sgm_dump;
                 if (dbase < D) {
-                    FVec<DPL> ov;
 #pragma unroll
-                    for (int i = 0; i < DPL; i++) ov.v[i] = o[i];
-                    if (SGM_NT & 2) {
-#pragma unroll
-                        for (int i = 0; i < DPL; i++)
-                            __builtin_nontemporal_store(o[i], sbase + (unsigned)dbase + i);
-                    } else {
-                        *reinterpret_cast<FVec<DPL> *>(sbase + dbase) = ov;
-                    }
+                    for (int i = 0; i < DPL; i++)
+                        __builtin_nontemporal_store(o[i], sbase + (unsigned)dbase + i);
                 }
             } else if (k < g.n && keep) {
                 {
@@ -796,8 +702,8 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
     // depends on and the compiler does not move LDS accesses of one iteration across another's; here,
     // right after the last writes, the ordering is made explicit (wavefront-scope release/acquire and a
     // wave barrier: no instruction with one wave per workgroup, a scheduling fence only).
-    if (WTA && g.n > 0) wave_sync();
-    if (WTA && PARK && g.n > 0) {
+    if (WTA && g.n > 0) {
+        wave_sync();
         // the last block's scan (its values are in buffer buf_last)
         const int buf = ((g.n - 1) / PF) & 1;
         const float *src = wbv + (buf * PF + wst) * RS + PF * wq;
@@ -809,17 +715,6 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
             if (v < b) { b = v; ba = DPL * PF * wq + t; }
         }
         if (wq == 0 && src[0] != src[0]) { b = -__builtin_inff(); ba = 0; }
-        wta_block_store<G>(b, ba, wpx[buf * PF + wst], wq, sd.disp);
-    } else if (WTA && g.n > 0) {
-        // the last block's merge (its partials are in buffer buf_last)
-        const int buf = ((g.n - 1) / PF) & 1;
-        float b = wbv[(buf * PF + wst) * WS + wq];
-        int ba = wba[(buf * PF + wst) * WS + wq];
-#pragma unroll
-        for (int t = 1; t < PF; t++) {
-            const int rs = (buf * PF + wst) * WS + t * G + (wq ^ (t & 4));
-            wta_merge(b, ba, wbv[rs], wba[rs]);
-        }
         wta_block_store<G>(b, ba, wpx[buf * PF + wst], wq, sd.disp);
     }
     if (!DU && kf >= 0) {

@@ -308,10 +308,6 @@ __device__ __forceinline__ void split3(float x, __bf16 &h, __bf16 &m, __bf16 &l)
     l = (__bf16)r2;
 }
 
-#ifndef XP_RING_F16
-#define XP_RING_F16 3
-#endif
-
 constexpr int XP_TY = 16, XP_TX = 32;             // output tile
 constexpr int XP_IY = XP_TY + 2, XP_IX = XP_TX + 2;
 constexpr int XP_NPIX = XP_IY * XP_IX;            // 612 input pixels per tile
@@ -320,17 +316,12 @@ constexpr int XP_STAGE = 6 * XP_PLANE;            // one c-block stage: 58,752 B
 constexpr int XP_UNITS = XP_NPIX * 4;             // (pixel, 4-channel chunk) units per stage
 constexpr int XP_STAGERS = 256;                   // threads of the stager waves
 constexpr int XP_UPT = (XP_UNITS + XP_STAGERS - 1) / XP_STAGERS;   // units per stager thread (10)
-// MFMA wave mapping: WR output rows x 64 / (8 / WR)... per wave -- WR = 8: one M-tile (32 output
-// channels) of 8 rows; WR = 4: both M-tiles of 4 rows (a pixel's 64 channels in one wave, as the
-// last layer's L2 norm wants).  8 accumulators either way.
-#ifndef XP_WR_MID
-#define XP_WR_MID 4
-#endif
-#ifndef XP_WR_FIRST
-#define XP_WR_FIRST 4
-#endif
-constexpr int XP_ACC = 8;                         // accumulators per MFMA wave
-#define XP_AL(F16, WR) (((WR) == 8 || (F16)) ? 2 : 1)   // A fragments requested this many taps ahead
+// MFMA wave mapping: each wave owns XP_WROWS output rows x both M-tiles (a pixel's 64 channels in one
+// wave, as the last layer's L2 norm wants): 8 accumulators.  (One M-tile of 8 rows per wave was
+// measured for the first and middle layers and not kept.)
+constexpr int XP_WROWS = 4, XP_MW = 2;
+constexpr int XP_ACC = XP_MW * XP_WROWS;          // accumulators per MFMA wave
+#define XP_AL(F16) ((F16) ? 2 : 1)                // A fragments requested this many taps ahead
 constexpr int XP_WX = XP_IX + 2, XP_WIN = (XP_IY + 2) * XP_WX;   // FIRST: image window of a tile (20 x 36)
 // two stages | FIRST: one image window per stager wave
 constexpr size_t XP_BIAS_OFF = (size_t)2 * XP_STAGE + 4 * XP_WIN * sizeof(float);
@@ -717,16 +708,15 @@ __device__ __forceinline__ void xp_st4(float4 v, __amdgpu_buffer_rsrc_t r, uint3
 // scheduler from hoisting more, which bounds the live registers (8 accumulators = 128 of the
 // 256 a wave may hold at 2 waves per SIMD).  A fragments (both M-tiles) are requested AL taps
 // ahead.  Rows past the output edge run on zero-filled input and are discarded by the epilogue.
-template <bool F16, int WR>
-__device__ __forceinline__ void xp_cblock(floatx16 (&acc)[XP_ACC], XpFrag (&a)[8 / WR],
-                                          XpFrag (&an)[XP_AL(F16, WR)][8 / WR], const uint4 *__restrict__ wf, int mt0,
+template <bool F16>
+__device__ __forceinline__ void xp_cblock(floatx16 (&acc)[XP_ACC], XpFrag (&a)[XP_MW],
+                                          XpFrag (&an)[XP_AL(F16)][XP_MW], const uint4 *__restrict__ wf, int mt0,
                                           int cb, int ncb, int lane, const char *sb)
 {
-    constexpr int XP_WROWS = WR, MW = 8 / WR;
     constexpr int NS = 9 * XP_WROWS;
     constexpr int NP = F16 ? 2 : 3;
-    constexpr int AL = XP_AL(F16, WR);
-    constexpr int RD = F16 ? XP_RING_F16 : 3;   // ring depth: fragments read RD-1 row-steps ahead
+    constexpr int AL = XP_AL(F16);
+    constexpr int RD = 3;   // ring depth: fragments read RD-1 row-steps ahead
     XpB ring[RD];
     auto boff = [&](int s) { return ((s / XP_WROWS / 3 + s % XP_WROWS) * XP_IX + (s / XP_WROWS) % 3) * 16; };
 #pragma unroll
@@ -737,7 +727,7 @@ __device__ __forceinline__ void xp_cblock(floatx16 (&acc)[XP_ACC], XpFrag (&a)[8
         if (r == 0 && tap > 0) {
             // a = A(tap); an[k] = A(tap + 1 + k); request A(tap + AL) (the next c-block's past tap 8)
 #pragma unroll
-            for (int m = 0; m < MW; m++) {
+            for (int m = 0; m < XP_MW; m++) {
                 a[m] = an[0][m];
 #pragma unroll
                 for (int k = 0; k + 1 < AL; k++) an[k][m] = an[k + 1][m];
@@ -749,7 +739,7 @@ __device__ __forceinline__ void xp_cblock(floatx16 (&acc)[XP_ACC], XpFrag (&a)[8
         __builtin_amdgcn_sched_barrier(0);
         const XpB &b = ring[s % RD];
 #pragma unroll
-        for (int m = 0; m < MW; m++) {
+        for (int m = 0; m < XP_MW; m++) {
             floatx16 &c = acc[m * XP_WROWS + r];
             if (F16) {
                 c = mfma_h(a[m].p[1], b.p[0], c);
@@ -768,7 +758,7 @@ __device__ __forceinline__ void xp_cblock(floatx16 (&acc)[XP_ACC], XpFrag (&a)[8
     }
     // hand the c-block boundary over: a = A(next c-block, tap 0)
 #pragma unroll
-    for (int m = 0; m < MW; m++) {
+    for (int m = 0; m < XP_MW; m++) {
         a[m] = an[0][m];
 #pragma unroll
         for (int k = 0; k + 1 < AL; k++) an[k][m] = an[k + 1][m];
@@ -807,7 +797,7 @@ __device__ __forceinline__ u32x4 xp_pair_parts(u32x2 hw, u32x2 lw)
     return u32x4{hw.x, hw.y, lw.x, lw.y};
 }
 
-// Tile epilogue of one MFMA wave (output rows WR*g .., M-tiles mt0 ..): bias (+ReLU | L2-normalise),
+// Tile epilogue of one MFMA wave (output rows XP_WROWS*g .., M-tiles mt0 ..): bias (+ReLU | L2-normalise),
 // stores, and (F16, !LAST) the running maximum of the stored outputs for the image's bound word
 // (one atomic per wave and image, xp_flush_amax).  unscale undoes the F16 power-of-two scalings.
 __device__ __forceinline__ void xp_flush_amax(uint32_t &amax_run, int &amax_img, int lane, float *out_amax,
@@ -823,7 +813,7 @@ __device__ __forceinline__ void xp_flush_amax(uint32_t &amax_run, int &amax_img,
 
 constexpr int XP_PIN = 4;   // a stored float4's registers are not rewritten before XP_PIN - 1 more stores issue
 
-template <bool LAST, bool OUT_CB, bool F16, int XP_WROWS, bool OSPL = false>
+template <bool LAST, bool OUT_CB, bool F16, bool OSPL = false>
 __device__ __forceinline__ void xp_epilogue(const floatx16 (&acc)[XP_ACC], int lane, int g, int mt0, int img,
                                             int ty0, int tx0, float unscale, const float4 *lbias4,
                                             float *__restrict__ out, int Hout, int Wout, const XpBatch &bt,
@@ -832,7 +822,6 @@ __device__ __forceinline__ void xp_epilogue(const floatx16 (&acc)[XP_ACC], int l
                                             float *__restrict__ out_amax, float oscale = 1.0f)
 {
     static_assert(!OSPL || (F16 && !LAST && !OUT_CB), "split outputs: F16 intermediate layers");
-    constexpr int MW = 8 / XP_WROWS;
     // ---- epilogue (MFMA waves): bias (+ReLU | L2-normalise) ------------
     // lane holds pixel column j, channels m*32 + 8q + 4h + e in acc[m * XP_WROWS + r][4q + e]
     // opaque copies of the lane coordinates: keep the epilogue's bias loads and
@@ -857,10 +846,10 @@ __device__ __forceinline__ void xp_epilogue(const floatx16 (&acc)[XP_ACC], int l
         // store still reads within XP_PIN instructions -- the store's issue and its data read are not
         // one event when MFMA waves contend for the VGPR read ports.  _isa_lint.py checks the built
         // code objects for this schedule.
-        constexpr int NPIN = MW * 2 * XP_WROWS * 2;
+        constexpr int NPIN = XP_MW * 2 * XP_WROWS * 2;
         u32x4 pin[NPIN];
 #pragma unroll
-        for (int m = 0; m < MW; m++) {
+        for (int m = 0; m < XP_MW; m++) {
             float4 b4[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) b4[q] = lbias4[((mt0 + m) * 32 + 8 * q + 4 * h) >> 2];
@@ -1043,15 +1032,15 @@ __global__ __launch_bounds__(512) void conv64_x6p_kernel(const float *__restrict
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const bool mfma_wave = wave < 4;            // waves 4..7 stage the input
-    constexpr int XP_WROWS = LAST ? 4 : (FIRST ? XP_WR_FIRST : XP_WR_MID), MW = 8 / XP_WROWS;
-    static_assert(XP_WROWS == 4 || XP_WROWS == 8, "wave mapping");
-    // MFMA wave: output rows XP_WROWS*g .. +XP_WROWS-1, M-tiles mt0 .. mt0+MW-1
+    // MFMA wave: output rows XP_WROWS*g .. +XP_WROWS-1, M-tiles mt0 .. mt0+XP_MW-1
     // wave-uniform by construction; readfirstlane tells the compiler (SGPR row offsets, scalar branches)
-    const int g = __builtin_amdgcn_readfirstlane(XP_WROWS == 4 ? (wave & 3) : ((wave >> 1) & 1));
-    const int mt0 = __builtin_amdgcn_readfirstlane(XP_WROWS == 4 ? 0 : (wave & 1));
+    const int g = __builtin_amdgcn_readfirstlane(wave & 3);
+    // always 0 (both M-tiles), but kept as an SGPR the compiler does not fold: with a literal 0 it forms the
+    // weight and output addresses differently, and the kernel's schedule is the measured one
+    const int mt0 = __builtin_amdgcn_readfirstlane(0);
     const int st = tid - XP_STAGERS;            // stager thread index (valid when !mfma_wave)
     constexpr int NP = F16 ? 2 : 3;
-    constexpr int AL = XP_AL(F16, XP_WROWS);
+    constexpr int AL = XP_AL(F16);
     const float *bias = wkblob;
     const uint4 *wf = reinterpret_cast<const uint4 *>(wkblob + (F16 ? LK_F16 : NF + LK_W));
     // B fragment: plane (part, h), input row XP_WROWS*g + r + ky, pixel j + kx
@@ -1083,9 +1072,9 @@ __global__ __launch_bounds__(512) void conv64_x6p_kernel(const float *__restrict
     float *lbias = reinterpret_cast<float *>(xsm + XP_BIAS_OFF);
     if (wave == 0) lbias[lane] = bias[lane];   // published by the first barrier below
     const float4 *lbias4 = reinterpret_cast<const float4 *>(lbias);
-    XpFrag a[MW], an[AL][MW];
+    XpFrag a[XP_MW], an[AL][XP_MW];
 #pragma unroll
-    for (int m = 0; m < MW; m++) {
+    for (int m = 0; m < XP_MW; m++) {
         a[m] = xp_afrag<NP>(wf, mt0 + m, 0, 0, lane);
 #pragma unroll
         for (int k = 0; k < AL; k++) an[k][m] = xp_afrag<NP>(wf, mt0 + m, 0, 1 + k, lane);
@@ -1106,7 +1095,7 @@ __global__ __launch_bounds__(512) void conv64_x6p_kernel(const float *__restrict
 #pragma unroll 1
         for (int cb = 0; cb < XP_NCB; cb++) {
             const int ncb = (cb + 1) & (XP_NCB - 1);
-            xp_cblock<F16, XP_WROWS>(acc, a, an, wf, mt0, cb, ncb, lane, xsm + cur * XP_STAGE + bbase);
+            xp_cblock<F16>(acc, a, an, wf, mt0, cb, ncb, lane, xsm + cur * XP_STAGE + bbase);
             if (cb == XP_NCB - 1) {
                 float unscale = 1.0f;
                 if (F16) {
@@ -1121,9 +1110,8 @@ __global__ __launch_bounds__(512) void conv64_x6p_kernel(const float *__restrict
                     }
                     oscale = osc;
                 }
-                xp_epilogue<LAST, OUT_CB, F16, XP_WROWS, OSPL>(acc, lane, g, mt0, img, ty0, tx0, unscale, lbias4, out,
-                                                               Hout, Wout, bt, ohi, olo, onrm, amax_run, amax_img,
-                                                               out_amax, oscale);
+                xp_epilogue<LAST, OUT_CB, F16, OSPL>(acc, lane, g, mt0, img, ty0, tx0, unscale, lbias4, out, Hout, Wout,
+                                                     bt, ohi, olo, onrm, amax_run, amax_img, out_amax, oscale);
             }
             __syncthreads();
             cur ^= 1;
@@ -1134,19 +1122,14 @@ __global__ __launch_bounds__(512) void conv64_x6p_kernel(const float *__restrict
 
 }  // namespace sde
 #include "tower_wino.h"
-// A/B timing builds substitute a probe copy of this header (tools/build_file_variant.sh -DSDE_H16_HEADER=...)
+// timing builds substitute a generated probe copy of this header (tools/variants/make_phase_header.py,
+// tools/build_file_variant.sh -DSDE_H16_HEADER=...)
 #ifdef SDE_H16_HEADER
 #include SDE_H16_HEADER
 #else
 #include "tower_h16.h"
 #endif
 #include "tower_h16q.h"
-#ifndef SDE_H16_L2
-#define SDE_H16_L2 1   // 0: layer 2 on conv64_x6p_kernel (32x32x16), for A/B builds
-#endif
-#ifndef SDE_H16Q
-#define SDE_H16Q 1   // 0: timing builds only -- middle split layers on conv64_h16_kernel's 8-wave form
-#endif
 namespace sde {
 
 
@@ -1541,63 +1524,6 @@ SDE_EXPORT int64_t sde_tower_workspace_bytes(int H, int W, int nlayers, int nf)
     return sde_tower_batch_workspace_bytes(H, W, 1, nlayers, nf);
 }
 
-static void set_tower_attrs()
-{
-    static std::atomic<uint64_t> done{0};
-    once_per_device(done, [] {
-    (void)hipFuncSetAttribute((const void *)conv64_mfma_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM);
-    (void)hipFuncSetAttribute((const void *)conv64_mfma_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM);
-    (void)hipFuncSetAttribute((const void *)conv64_mfma_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM);
-    (void)hipFuncSetAttribute((const void *)conv64_mfma_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM);
-#define SDE_X6P_ATTR1(F, L, I, O, H) (void)hipFuncSetAttribute((const void *)conv64_x6p_kernel<F, L, I, O, H>, \
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, XP_SMEM)
-#define SDE_X6P_ATTR(F, L, I, O) SDE_X6P_ATTR1(F, L, I, O, false); SDE_X6P_ATTR1(F, L, I, O, true)
-    SDE_X6P_ATTR(true, false, false, true);
-    SDE_X6P_ATTR(true, false, false, false);
-    SDE_X6P_ATTR(true, true, false, false);
-    SDE_X6P_ATTR(false, false, true, true);
-    SDE_X6P_ATTR(false, false, false, false);
-    SDE_X6P_ATTR(false, false, true, false);
-    SDE_X6P_ATTR(false, false, false, true);
-    SDE_X6P_ATTR(false, true, true, false);
-    SDE_X6P_ATTR(false, true, false, false);
-    (void)hipFuncSetAttribute((const void *)conv64_x6p_kernel<true, false, false, false, true, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, XP_SMEM);
-#undef SDE_X6P_ATTR1
-#undef SDE_X6P_ATTR
-#define SDE_H16_ATTR(L, I, O, S, ...) (void)hipFuncSetAttribute((const void *)conv64_h16_kernel<L, I, O, S, ##__VA_ARGS__>, \
-                                                                hipFuncAttributeMaxDynamicSharedMemorySize, H16_SMEM)
-    SDE_H16_ATTR(false, false, false, false, true, true);
-    (void)hipFuncSetAttribute((const void *)conv64_h16q_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, H16_SMEM);
-    (void)hipFuncSetAttribute((const void *)conv64_h16_kernel<false, false, true, false, false, false, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, H16_SMEM_FIRST);
-    (void)hipFuncSetAttribute((const void *)conv64_h16_kernel<false, false, false, false, false, false, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, H16_SMEM_FIRST);
-    (void)hipFuncSetAttribute((const void *)conv64_h16_kernel<false, false, false, false, false, true, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, H16_SMEM_FIRST);
-    SDE_H16_ATTR(true, false, false, false, true, false);
-    SDE_H16_ATTR(true, false, false, true, true, false);
-    SDE_H16_ATTR(true, true, false, false);
-    SDE_H16_ATTR(true, false, false, false);
-    SDE_H16_ATTR(true, true, false, true);
-    SDE_H16_ATTR(true, false, false, true);
-    SDE_H16_ATTR(false, true, true, false);
-    SDE_H16_ATTR(false, true, false, false);
-    SDE_H16_ATTR(false, false, true, false);
-    SDE_H16_ATTR(false, false, false, false);
-#undef SDE_H16_ATTR
-#define SDE_WINO_ATTR(L, I, O) (void)hipFuncSetAttribute((const void *)wino_kernel<L, I, O>, \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, WN_SMEM)
-    SDE_WINO_ATTR(true, true, false);
-    SDE_WINO_ATTR(true, false, false);
-    SDE_WINO_ATTR(false, true, true);
-    SDE_WINO_ATTR(false, true, false);
-    SDE_WINO_ATTR(false, false, true);
-    SDE_WINO_ATTR(false, false, false);
-#undef SDE_WINO_ATTR
-    });
-}
-
 // Persistent tower grids: one workgroup per CU (160 KB of LDS each), or g_grid_cus workgroups when set
 // (sde_set_persistent_grid: the tower sharing the device with other work on CU-masked streams, where a
 // workgroup per device CU would leave the last ones waiting for CUs the other stream holds).
@@ -1617,6 +1543,20 @@ static int cu_count()
     return g > 0 ? std::min(g, cached[dev]) : cached[dev];
 }
 
+// The tile space of a batch launch (tw x th output tiles, image-major) and the persistent grid that walks it
+static int xp_batch(XpBatch &bt, int tw, int th, int hout, int wout, int nimg, int64_t in_stride, int64_t out_stride,
+                    int amax_stride)
+{
+    bt.tiles_x = cdiv(wout, tw);
+    bt.tiles_img = bt.tiles_x * cdiv(hout, th);
+    bt.ntiles = bt.tiles_img * nimg;
+    bt.in_stride = in_stride;
+    bt.out_stride = out_stride;
+    bt.pix_stride = (int64_t)hout * wout;
+    bt.amax_stride = amax_stride;
+    return std::min(bt.ntiles, cu_count());
+}
+
 // One launch: layer == 2 -> conv1+conv2 fused from the padded image (Hin x Win floats);
 // layer > 2 -> one 64->64 conv on Hin x Win x 64 activations.  Output (Hin-4|Hin-2) x ... x 64.
 // in_cb / out_cb: activations in the c-block-major layout [4][h][w][16] (bf16x6 / f16x3 paths).
@@ -1629,10 +1569,11 @@ static void launch_layer(const float *in, int Hin, int Win, const float *packed,
                          const float *in_amax, float *out_amax, hipStream_t st, int nimg = 1, int64_t in_stride = 0,
                          int64_t out_stride = 0, int amax_stride = 0, bool in_sp = false, bool out_sp = false)
 {
-    set_tower_attrs();
     const bool last = (layer == nlayers);
     const bool f16 = (flags & SDE_TOWER_F16X3) != 0;
     const bool x6 = f16 || (flags & SDE_TOWER_BF16X6) != 0;
+    const bool h16 = f16 && !(flags & SDE_TOWER_MFMA32);   // v_mfma_f32_16x16x32_f16 (tower_h16.h)
+    const bool split = ohi || olo || onrm;
     const float *w1 = packed;
     const float *wk = packed + L1_FLOATS + (int64_t)(layer - 2) * LK_FLOATS;
     const int hout = Hin - (layer == 2 ? 4 : 2), wout = Win - (layer == 2 ? 4 : 2);
@@ -1641,94 +1582,53 @@ static void launch_layer(const float *in, int Hin, int Win, const float *packed,
     // rebases its descriptors per tile (same f16x3 arithmetic, fp32-level error either way)
     const bool wino_fits = (int64_t)Hin * Win * 256 < ((int64_t)1 << 32) &&
                            (int64_t)hout * wout * 256 < ((int64_t)1 << 32);
-    if (f16 && layer >= 3 && !ohi && !onrm && (flags & SDE_TOWER_WINOGRAD) && wino_fits) {
+    const bool wino = f16 && layer >= 3 && !ohi && !onrm && (flags & SDE_TOWER_WINOGRAD) && wino_fits;
+    XpBatch bt;   // the persistent kernels' tile space (unused by the fp32 kernel)
+    const int grid = xp_batch(bt, wino ? WN_TX : XP_TX, wino ? WN_TY : XP_TY, hout, wout, nimg, in_stride, out_stride,
+                              amax_stride);
+    // Every tower instantiation in the library is named below, once, with its dynamic-LDS size: launch_lds
+    // opts the kernel into that size on its first launch per device.
+    if (wino) {
         // Winograd F(2x2, 3x3) for the 64 -> 64 layers (tower_wino.h)
-        XpBatch bt;
-        bt.tiles_x = cdiv(wout, WN_TX);
-        bt.tiles_img = bt.tiles_x * cdiv(hout, WN_TY);
-        bt.ntiles = bt.tiles_img * nimg;
-        bt.in_stride = in_stride;
-        bt.out_stride = out_stride;
-        bt.pix_stride = (int64_t)hout * wout;
-        bt.amax_stride = amax_stride;
-        const int grid = std::min(bt.ntiles, cu_count());
-#define SDE_WINO(L, I, O) wino_kernel<L, I, O><<<grid, 512, WN_SMEM, st>>>(in, Hin, Win, wk, out, hout, wout, bt, \
-                                                                          in_amax, out_amax)
+#define SDE_WINO(L, I, O) \
+    launch_lds<wino_kernel<L, I, O>, WN_SMEM>(grid, 512, st, in, Hin, Win, wk, out, hout, wout, bt, in_amax, out_amax)
         if (last) { if (in_cb) SDE_WINO(true, true, false); else SDE_WINO(true, false, false); }
         else if (in_cb) { if (out_cb) SDE_WINO(false, true, true); else SDE_WINO(false, true, false); }
         else { if (out_cb) SDE_WINO(false, false, true); else SDE_WINO(false, false, false); }
 #undef SDE_WINO
-        return;
-    }
-    if (f16 && layer == 2 && !last && !(flags & SDE_TOWER_MFMA32) && SDE_H16_L2) {
-        // layer 2 (conv1 on the stagers + conv2) on v_mfma_f32_16x16x32_f16 (tower_h16.h)
-        XpBatch bt;
-        bt.tiles_x = cdiv(wout, XP_TX);
-        bt.tiles_img = bt.tiles_x * cdiv(hout, XP_TY);
-        bt.ntiles = bt.tiles_img * nimg;
-        bt.in_stride = in_stride;
-        bt.out_stride = out_stride;
-        bt.pix_stride = (int64_t)hout * wout;
-        bt.amax_stride = amax_stride;
-        const int grid = std::min(bt.ntiles, cu_count());
-        if (out_sp)
-            conv64_h16_kernel<false, false, false, false, false, true, true><<<grid, 512, H16_SMEM_FIRST, st>>>(
-                in, Hin, Win, wk, out, hout, wout, nullptr, nullptr, nullptr, bt, in_amax, out_amax, w1);
-        else if (out_cb)
-            conv64_h16_kernel<false, false, true, false, false, false, true><<<grid, 512, H16_SMEM_FIRST, st>>>(
-                in, Hin, Win, wk, out, hout, wout, nullptr, nullptr, nullptr, bt, in_amax, out_amax, w1);
-        else
-            conv64_h16_kernel<false, false, false, false, false, false, true><<<grid, 512, H16_SMEM_FIRST, st>>>(
-                in, Hin, Win, wk, out, hout, wout, nullptr, nullptr, nullptr, bt, in_amax, out_amax, w1);
-        return;
-    }
-    if (f16 && layer >= 3 && !(flags & SDE_TOWER_MFMA32)) {
-        // the 64 -> 64 layers on v_mfma_f32_16x16x32_f16 (tower_h16.h; same tiles as the direct kernel)
-        XpBatch bt;
-        bt.tiles_x = cdiv(wout, XP_TX);
-        bt.tiles_img = bt.tiles_x * cdiv(hout, XP_TY);
-        bt.ntiles = bt.tiles_img * nimg;
-        bt.in_stride = in_stride;
-        bt.out_stride = out_stride;
-        bt.pix_stride = (int64_t)hout * wout;
-        bt.amax_stride = amax_stride;
-        const int grid = std::min(bt.ntiles, cu_count());
-#define SDE_H16(L, I, O, S, ...) conv64_h16_kernel<L, I, O, S, ##__VA_ARGS__><<<grid, 512, H16_SMEM, st>>>( \
-        in, Hin, Win, wk, out, hout, wout, (S) ? ohi : nullptr, (S) ? olo : nullptr, (S) ? onrm : nullptr, bt, in_amax, out_amax, \
-        nullptr)
-        const bool split = ohi || olo || onrm;
-        if (in_sp) {   // split activations in (and out, below the last layer): LDS-DMA stagers
-            if (!last && SDE_H16Q)   // the 4-wave kernel with resident weights (tower_h16q.h)
-                conv64_h16q_kernel<<<grid, 256, H16_SMEM, st>>>(in, Hin, Win, wk, out, hout, wout, bt, in_amax, out_amax);
-            else if (!last) SDE_H16(false, false, false, false, true, true);
-            else if (split) SDE_H16(true, false, false, true, true, false);
-            else SDE_H16(true, false, false, false, true, false);
-            return;
+    } else if (h16 && (layer >= 3 || !last)) {
+        // conv64_h16_kernel<LAST, IN_CB, OUT_CB, SPLIT, ISPL, OSPL, FIRST> (same tiles as the direct kernel)
+#define SDE_H16(SM, L, I, O, S, ...)                                                                                \
+    launch_lds<conv64_h16_kernel<L, I, O, S, ##__VA_ARGS__>, SM>(grid, 512, st, in, Hin, Win, wk, out, hout, wout,   \
+                                                                 (S) ? ohi : nullptr, (S) ? olo : nullptr,            \
+                                                                 (S) ? onrm : nullptr, bt, in_amax, out_amax,         \
+                                                                 layer == 2 ? w1 : nullptr)
+        if (layer == 2) {   // conv1 on the stagers + conv2
+            if (out_sp) SDE_H16(H16_SMEM_FIRST, false, false, false, false, false, true, true);
+            else if (out_cb) SDE_H16(H16_SMEM_FIRST, false, false, true, false, false, false, true);
+            else SDE_H16(H16_SMEM_FIRST, false, false, false, false, false, false, true);
+        } else if (in_sp) {   // split activations in (and out, below the last layer): LDS-DMA stagers
+            if (!last)   // the 4-wave kernel with resident weights (tower_h16q.h)
+                launch_lds<conv64_h16q_kernel, H16_SMEM>(grid, 256, st, in, Hin, Win, wk, out, hout, wout, bt, in_amax,
+                                                         out_amax);
+            else if (split) SDE_H16(H16_SMEM, true, false, false, true, true, false);
+            else SDE_H16(H16_SMEM, true, false, false, false, true, false);
+        } else if (last) {
+            if (split) { if (in_cb) SDE_H16(H16_SMEM, true, true, false, true); else SDE_H16(H16_SMEM, true, false, false, true); }
+            else { if (in_cb) SDE_H16(H16_SMEM, true, true, false, false); else SDE_H16(H16_SMEM, true, false, false, false); }
+        } else if (in_cb) {
+            if (out_cb) SDE_H16(H16_SMEM, false, true, true, false); else SDE_H16(H16_SMEM, false, true, false, false);
+        } else {
+            if (out_cb) SDE_H16(H16_SMEM, false, false, true, false); else SDE_H16(H16_SMEM, false, false, false, false);
         }
-        if (last && split) { if (in_cb) SDE_H16(true, true, false, true); else SDE_H16(true, false, false, true); }
-        else if (last) { if (in_cb) SDE_H16(true, true, false, false); else SDE_H16(true, false, false, false); }
-        else if (in_cb) { if (out_cb) SDE_H16(false, true, true, false); else SDE_H16(false, true, false, false); }
-        else { if (out_cb) SDE_H16(false, false, true, false); else SDE_H16(false, false, false, false); }
 #undef SDE_H16
-        return;
-    }
-    if (x6) {
-        XpBatch bt;
-        bt.tiles_x = cdiv(wout, XP_TX);
-        bt.tiles_img = bt.tiles_x * cdiv(hout, XP_TY);
-        bt.ntiles = bt.tiles_img * nimg;
-        bt.in_stride = in_stride;
-        bt.out_stride = out_stride;
-        bt.pix_stride = (int64_t)hout * wout;
-        bt.amax_stride = amax_stride;
-        const int grid = std::min(bt.ntiles, cu_count());
-#define SDE_X6P(F, L, I, O, H, ...) conv64_x6p_kernel<F, L, I, O, H, ##__VA_ARGS__><<<grid, 512, XP_SMEM, st>>>( \
-        in, Hin, Win, (F) ? w1 : nullptr, wk, out, hout, wout, (L) ? ohi : nullptr, (L) ? olo : nullptr, \
-        (L) ? onrm : nullptr, bt, in_amax, out_amax)
-        if (out_sp) {   // layer 2 writing split activations (f16x3; the callers check)
-            SDE_X6P(true, false, false, false, true, true);
-            return;
-        }
+    } else if (x6) {
+        // conv64_x6p_kernel<FIRST, LAST, IN_CB, OUT_CB, F16, OSPL>
+#define SDE_X6P(F, L, ...)                                                                                         \
+    launch_lds<conv64_x6p_kernel<F, L, __VA_ARGS__>, XP_SMEM>(grid, 512, st, in, Hin, Win, (F) ? w1 : nullptr, wk,  \
+                                                              out, hout, wout, (L) ? ohi : nullptr,                  \
+                                                              (L) ? olo : nullptr, (L) ? onrm : nullptr, bt,         \
+                                                              in_amax, out_amax)
 #define SDE_X6P_ALL(H)                                                      \
         if (layer == 2) {                                                   \
             if (last) SDE_X6P(true, true, false, false, H);                 \
@@ -1743,23 +1643,27 @@ static void launch_layer(const float *in, int Hin, int Win, const float *packed,
             else if (out_cb) SDE_X6P(false, false, false, true, H);         \
             else SDE_X6P(false, false, false, false, H);                    \
         }
-        if (f16) { SDE_X6P_ALL(true) } else { SDE_X6P_ALL(false) }
+        // out_sp: layer 2 writing split activations (f16x3; the callers check)
+        if (out_sp) SDE_X6P(true, false, false, false, true, true);
+        else if (f16) { SDE_X6P_ALL(true) } else { SDE_X6P_ALL(false) }
 #undef SDE_X6P_ALL
 #undef SDE_X6P
-        return;
-    }
-    dim3 grid(cdiv(wout, TW_TX), cdiv(hout, TW_TY));
-    const int64_t pix = (int64_t)hout * wout;
-    for (int i = 0; i < nimg; i++) {
-        const float *ini = in + i * in_stride;
-        float *outi = out + i * out_stride;
-        uint16_t *hi = ohi ? ohi + i * pix * NF : nullptr, *lo = olo ? olo + i * pix * NF : nullptr;
-        float *nr = onrm ? onrm + i * pix : nullptr;
-#define SDE_CONV(K, F, L, SM) K<F, L><<<grid, 512, SM, st>>>(ini, Hin, Win, (F) ? w1 : nullptr, wk, outi, hout, wout, \
-                                                             (L) ? hi : nullptr, (L) ? lo : nullptr, (L) ? nr : nullptr)
-        if (layer == 2) { if (last) SDE_CONV(conv64_mfma_kernel, true, true, TW_SMEM); else SDE_CONV(conv64_mfma_kernel, true, false, TW_SMEM); }
-        else { if (last) SDE_CONV(conv64_mfma_kernel, false, true, TW_SMEM); else SDE_CONV(conv64_mfma_kernel, false, false, TW_SMEM); }
+    } else {
+        // fp32: one launch per image
+        const dim3 grid2(cdiv(wout, TW_TX), cdiv(hout, TW_TY));
+        const int64_t pix = (int64_t)hout * wout;
+        for (int i = 0; i < nimg; i++) {
+            const float *ini = in + i * in_stride;
+            float *outi = out + i * out_stride;
+            uint16_t *hi = ohi ? ohi + i * pix * NF : nullptr, *lo = olo ? olo + i * pix * NF : nullptr;
+            float *nr = onrm ? onrm + i * pix : nullptr;
+#define SDE_CONV(F, L)                                                                                              \
+    launch_lds<conv64_mfma_kernel<F, L>, TW_SMEM>(grid2, 512, st, ini, Hin, Win, (F) ? w1 : nullptr, wk, outi, hout, \
+                                                  wout, (L) ? hi : nullptr, (L) ? lo : nullptr, (L) ? nr : nullptr)
+            if (layer == 2) { if (last) SDE_CONV(true, true); else SDE_CONV(true, false); }
+            else { if (last) SDE_CONV(false, true); else SDE_CONV(false, false); }
 #undef SDE_CONV
+        }
     }
 }
 

@@ -20,10 +20,10 @@
 // * B fragment of (tap, row, half): lane l reads plane (part, l >> 4) at pixel (row + ky,
 //   16 half + (l & 15) + kx): one conflict-free ds_read_b128, a per-lane base plus an immediate;
 // * A fragments come straight from the F16 weight blob's [mtile][cblock16][tap][part][lane][8]
-//   layout (no new packing): lane l of quarter q reads 16 B at a per-lane offset, from L2 -- by
-//   default (h16_cblock12) a whole tap (4 quarters) one tap ahead, so each B fragment pair feeds 12
-//   MFMAs; h16_cblock (H16_B12=0, and the last layer with split outputs) works in half-taps
-//   (2 quarters each, 6 MFMAs per B pair) requested two half-taps ahead;
+//   layout (no new packing): lane l of quarter q reads 16 B at a per-lane offset, from L2 -- in
+//   h16_cblock12 a whole tap (4 quarters) one tap ahead, so each B fragment pair feeds 12 MFMAs; the
+//   last layer with split outputs alone (its epilogue would spill) uses h16_cblock, which works in
+//   half-taps (2 quarters each, 6 MFMAs per B pair) requested two half-taps ahead;
 // * layer 2 (FIRST): the stagers compute conv1 from the tile's image window in LDS;
 // * epilogue: a lane holds channels 16q + 4(l >> 4) .. +3 of pixel (l & 15): one dwordx4 store
 //   per (row, half, quarter); the c-block-major output [cblk16][h][w][16] is written as 1 KB
@@ -47,17 +47,14 @@ static_assert(H16_SMEM <= 163840, "LDS");
 constexpr size_t H16_WIN_OFF = H16_SMEM;
 constexpr size_t H16_SMEM_FIRST = H16_WIN_OFF + XP_WIN * sizeof(float);   // 162,880 B
 static_assert(H16_SMEM_FIRST <= 163840, "LDS (layer 2)");
-// Timing-only diagnostic builds (no epilogue stores, no stager work, constant A or B operands, in-kernel
-// clock stamps, ring-depth probes; wrong results) live in the probe copy tools/variants/tower_h16_diag.h,
-// which tools/build_file_variant.sh substitutes for this header (-DSDE_H16_HEADER=...).
+// Timing-only builds substitute a generated probe copy of this header (in-kernel clock stamps:
+// tools/variants/make_phase_header.py; tools/build_file_variant.sh -DSDE_H16_HEADER=...).
 // Cache-policy bits of the stagers' activation loads: 1 (sc0) streams each activation past the CU's L1,
 // which leaves the L1 to the A fragments all four MFMA waves re-read every tap.  Timing builds showed the
 // MFMA waves waiting on those fragments (a probe build with the same loads issued but not consumed runs 149 us
 // like no loads at all, 151, against 204 us).  Tower pair -8 to -30 us in three round-robin runs
-// (profiles/r05/tower_act_aux_nt.txt); 2 (nt) does not help; 0 = the default policy.
-#ifndef H16_ACT_AUX
-#define H16_ACT_AUX 1
-#endif
+// (profiles/r05/tower_act_aux_nt.txt); 2 (nt) did not help.
+constexpr int H16_ACT_AUX = 1;
 
 // Split 4 channels, scaled by s, into the stage's (part, quarter) planes at dst (the unit's byte offset
 // in the stage, see h16_stager_loop): hi = f16(x s) by packed converts, lo = f16(x s - hi) by v_fma_mix from the
@@ -405,7 +402,7 @@ __device__ __forceinline__ void h16_cblock(floatx4 (&acc)[32], H16A (&abuf)[NA],
     }
 }
 
-// The same c-block with each B fragment feeding all four quarters (H16_B12): 9 taps x 8 (row, half) steps of
+// The same c-block with each B fragment feeding all four quarters: 9 taps x 8 (row, half) steps of
 // 12 MFMAs, so half the B reads from LDS per MFMA.  A ring of two whole taps (four half-tap slots, abuf[(h +
 // PH) % 4] for half-tap h; 18 half-taps per c-block, so the two c-blocks of a tile run in phases 0 and 2):
 // tap s requests tap s + 1 into the slots tap s - 1 left; on exit abuf holds A(ncb, tap 0) at phase PH + 2.
@@ -422,8 +419,8 @@ __device__ __forceinline__ H16B h16_bfrag12(const char *sb, int b)
 
 // BRD: depth of the B ring (fragments read BRD - 1 (row, half) steps ahead).  Depth 3 (two steps, 24 MFMAs
 // ahead) takes the MFMA waves' c-block loop from 280 to 249-274 kcycles per launch against the 232-kcycle MFMA floor
-// (phase stamps, profiles/r06/tower_phase_*.txt): the LDS latency of a one-step-ahead read was showing.  The 8
-// more VGPRs fit the middle layers' c-block-layout instantiation without spills; the others keep depth 2.
+// (phase stamps, profiles/r06/tower_phase_*.txt): the LDS latency of a one-step-ahead read was showing.  Every
+// instantiation that uses this c-block runs depth 3 (BRD in conv64_h16_kernel).
 // NEXT = false (the c-block that ends a tile): the last tap does not request the next c-block's first tap; the
 // caller's epilogue does, once half the accumulators are stored (h16_epilogue's `mid`), so those 32 VGPRs are not
 // live across the whole epilogue -- what lets the 3-deep B ring fit layer 2 and the last layer without spills.
@@ -465,11 +462,6 @@ __device__ __forceinline__ void h16_cblock12(floatx4 (&acc)[32], H16A (&abuf)[4]
         }
     }
 }
-// 2: every layer but the last one with split outputs (whose epilogue would spill), 1: the middle layers only,
-// 0: none (A/B builds)
-#ifndef H16_B12
-#define H16_B12 2
-#endif
 
 // Tile epilogue of one MFMA wave (rows 4g ..): unscale + bias, then ReLU + c-block-major stores
 // (+ the running bound word), or (LAST) the L2 norm and [h][w][64] stores.  Stored registers are
@@ -690,7 +682,7 @@ __global__ __launch_bounds__(512) void conv64_h16_kernel(const float *__restrict
     const int bbase = (lane >> 4) * H16_PLANE + ((4 * g) * XP_IX + (lane & 15)) * 16;
     // c-blocks feeding each B fragment to all four quarters (h16_cblock12), except the last layer with
     // split outputs (its epilogue would spill 13 VGPRs with the 2-tap A ring)
-    constexpr bool B12 = H16_B12 == 2 ? !(LAST && SPLIT) : H16_B12 == 1 ? !LAST && !FIRST : false;
+    constexpr bool B12 = !(LAST && SPLIT);
     constexpr int BRD = 3;
     H16A abuf[4];   // h16_cblock: slots 0-2
     abuf[0] = h16_afrag(ra, avoff, 0, 0);

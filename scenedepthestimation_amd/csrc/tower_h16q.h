@@ -61,39 +61,34 @@ __device__ __forceinline__ void h16_dma_offsets(int Win, int lane, uint32_t (&vo
     }
 }
 
-// Work split (H16Q_NQ output-channel quarters x H16Q_NR rows per wave, NQ * NR = 16): NQ = 1 -- wave g owns
-// quarter g, all 16 rows (each B fragment feeds 3 MFMAs, A 144 registers); NQ = 2 -- wave g owns quarters
-// 2 (g & 1) + {0, 1} of rows 8 (g >> 1) .. + 7 (each B fragment feeds 6 MFMAs, half the LDS reads, but A
-// takes 288 registers: 119 VGPRs spill at 512, so not built by default).
-#ifndef H16Q_NQ
-#define H16Q_NQ 1
-#endif
-constexpr int H16Q_NR = 16 / H16Q_NQ;
-__device__ __forceinline__ int h16q_q0(int g) { return H16Q_NQ == 1 ? g : 2 * (g & 1); }
-__device__ __forceinline__ int h16q_r0(int g) { return H16Q_NQ == 1 ? 0 : H16Q_NR * (g >> 1); }
+// Work split: wave g owns output-channel quarter g, all 16 rows of the tile (each B fragment feeds 3 MFMAs,
+// A takes 144 registers).  Two quarters x 8 rows per wave (half the LDS reads) was measured and not kept:
+// its 288 A registers spill 119 VGPRs.
+constexpr int H16Q_NR = 16;
+// The epilogue and the bias load keep that experiment's loop over a wave's quarters, now one trip: without
+// the loops the compiler orders the kernel's instructions differently, and this kernel's schedule is the
+// measured one.
+constexpr int H16Q_NQ = 1;
 
-// A fragments of wave g: [cb][tap][part][quarter], 16 B each (8 fp16 of the lane's k slots for output
-// channel 16 (q0 + qq) + (l & 15)) from the F16 blob's [mtile][cblock16][tap][part][lane][8] order.
+// A fragments of wave g: [cb][tap][part], 16 B each (8 fp16 of the lane's k slots for output channel
+// 16 g + (l & 15)) from the F16 blob's [mtile][cblock16][tap][part][lane][8] order.
 struct H16QA {
-    f16x8 f[2][9][2][H16Q_NQ];
+    f16x8 f[2][9][2];
 };
 
 __device__ __forceinline__ void h16q_load_a(H16QA &a, const float *__restrict__ wkblob, int g, int lane)
 {
     const __amdgpu_buffer_rsrc_t ra = xp_rsrc(wkblob + LK_F16);
-    const int q0 = h16q_q0(g);
-    const int ln = ((lane >> 4) & 1) * 32 + 16 * (q0 & 1) + (lane & 15);
-    const uint32_t voff = (uint32_t)(((q0 >> 1) * XP_NCB + (lane >> 5)) * 18 * 64 + ln) * 16u;
+    const int ln = ((lane >> 4) & 1) * 32 + 16 * (g & 1) + (lane & 15);
+    const uint32_t voff = (uint32_t)(((g >> 1) * XP_NCB + (lane >> 5)) * 18 * 64 + ln) * 16u;
 #pragma unroll
     for (int cb = 0; cb < 2; cb++)
 #pragma unroll
         for (int tap = 0; tap < 9; tap++)
 #pragma unroll
             for (int p = 0; p < 2; p++)
-#pragma unroll
-                for (int qq = 0; qq < H16Q_NQ; qq++)   // quarter q0 + 1: the next 16 lanes of the M-tile
-                    a.f[cb][tap][p][qq] = __builtin_bit_cast(
-                        f16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, voff, cb * H16_A_CB + (tap * 2 + p) * 1024 + 256 * qq, 0));
+                a.f[cb][tap][p] = __builtin_bit_cast(
+                    f16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, voff, cb * H16_A_CB + (tap * 2 + p) * 1024, 0));
 }
 
 // B fragment of step b = (tap, row r, half ph); sb = the stage at the lane's base (plane lane >> 4, pixel
@@ -110,7 +105,7 @@ __device__ __forceinline__ H16B h16q_bfrag(const char *sb, int b)
 
 constexpr int H16Q_RD = 4;   // B ring depth
 
-// one c-block of one wave: 9 taps x NR rows x 2 halves, 3 MFMAs per quarter each, acc[(r * 2 + ph) * NQ + qq]
+// one c-block of one wave: 9 taps x NR rows x 2 halves, 3 MFMAs each, acc[r * 2 + ph]
 template <int CB>
 __device__ __forceinline__ void h16q_cblock(floatx4 (&acc)[32], const H16QA &a, const char *sb)
 {
@@ -123,13 +118,10 @@ __device__ __forceinline__ void h16q_cblock(floatx4 (&acc)[32], const H16QA &a, 
         __builtin_amdgcn_sched_barrier(0);
         const int tap = b / (2 * H16Q_NR);
         const H16B &bf = ring[b % H16Q_RD];
-#pragma unroll
-        for (int qq = 0; qq < H16Q_NQ; qq++) {
-            floatx4 &c = acc[(b % (2 * H16Q_NR)) * H16Q_NQ + qq];
-            c = mfma16(a.f[CB][tap][1][qq], bf.hi, c);
-            c = mfma16(a.f[CB][tap][0][qq], bf.lo, c);
-            c = mfma16(a.f[CB][tap][0][qq], bf.hi, c);
-        }
+        floatx4 &c = acc[b % (2 * H16Q_NR)];
+        c = mfma16(a.f[CB][tap][1], bf.hi, c);
+        c = mfma16(a.f[CB][tap][0], bf.lo, c);
+        c = mfma16(a.f[CB][tap][0], bf.hi, c);
         if (b + H16Q_RD - 1 < NB) ring[(b + H16Q_RD - 1) % H16Q_RD] = h16q_bfrag(sb, b + H16Q_RD - 1);
     }
 }
@@ -149,29 +141,28 @@ __device__ __forceinline__ void h16q_epilogue(const floatx4 (&acc)[32], int lane
     asm volatile("" : "+v"(j), "+v"(k4));
     const size_t HW = (size_t)Hout * Wout;
     const uint32_t pb = (uint32_t)HW * 16u;
-    const int q0 = h16q_q0(g), r0 = h16q_r0(g);
     // channels 16q + 4 k4 + e: 8-channel group 2q + (k4 >> 1), plane (q >> 1) * 8 + part * 4 + 2 (q & 1) + (k4 >> 1)
     const uint32_t lane_pl = (uint32_t)((k4 & 1) * 4 + (k4 >> 1)) * pb;
     char *outi = reinterpret_cast<char *>(out + img * bt.out_stride);
     u32x4 pin[32];
 #pragma unroll
     for (int qq = 0; qq < H16Q_NQ; qq++) {
-        const int q = q0 + qq;
+        const int q = g + qq;
         const __amdgpu_buffer_rsrc_t rs =
-            xp_rsrc(outi + ((size_t)((q >> 1) * 8 + 2 * (q & 1)) * HW + (size_t)(ty0 + r0) * Wout) * 16);
+            xp_rsrc(outi + ((size_t)((q >> 1) * 8 + 2 * (q & 1)) * HW + (size_t)ty0 * Wout) * 16);
         // the outputs scaled by 2^sigma straight from the accumulators (scale folded into the unscale and
         // the bias: exact), their bound unscaled at the end
         const float bq[4] = {b4[qq].x * oscale, b4[qq].y * oscale, b4[qq].z * oscale, b4[qq].w * oscale};
         const float us = unscale * oscale;
 #pragma unroll
         for (int r = 0; r < H16Q_NR; r++) {
-            const bool rok = ty0 + r0 + r < Hout;
+            const bool rok = ty0 + r < Hout;
             const uint32_t so = (uint32_t)(r * Wout) * 16u;
 #pragma unroll
             for (int ph = 0; ph < 2; ph++) {
                 const int x = tx0 + 16 * ph + j;
                 const bool ok = rok && x < Wout;
-                const floatx4 &c = acc[(r * 2 + ph) * H16Q_NQ + qq];
+                const floatx4 &c = acc[r * 2 + ph];
                 float o4[4];
 #pragma unroll
                 for (int e = 0; e < 4; e++) o4[e] = fmaxf(fmaf(c[e], us, bq[e]), 0.f);
@@ -182,7 +173,7 @@ __device__ __forceinline__ void h16q_epilogue(const floatx4 (&acc)[32], int lane
                 }
                 u32x2 hw2, lw2;
                 xp_split16s(o, hw2, lw2);
-                const int k = (qq * H16Q_NR + r) * 2 + ph;
+                const int k = r * 2 + ph;
                 pin[k] = xp_pair_parts<false>(hw2, lw2);
                 __builtin_amdgcn_raw_buffer_store_b128(pin[k], rs, ok ? lane_pl + (uint32_t)x * 16u : XP_OOB, so, 0);
                 if (k >= XP_PIN - 1) asm volatile("" ::"v"(pin[k - (XP_PIN - 1)]));
@@ -220,8 +211,8 @@ __global__ __launch_bounds__(256) void conv64_h16q_kernel(const float *__restric
     float4 b4[H16Q_NQ];
 #pragma unroll
     for (int qq = 0; qq < H16Q_NQ; qq++)
-        b4[qq] = *reinterpret_cast<const float4 *>(wkblob + 16 * (h16q_q0(g) + qq) + 4 * (lane >> 4));
-    const char *bbase = hsm + (lane >> 4) * H16_PLANE + (h16q_r0(g) * XP_IX + (lane & 15)) * 16;
+        b4[qq] = *reinterpret_cast<const float4 *>(wkblob + 16 * (g + qq) + 4 * (lane >> 4));
+    const char *bbase = hsm + (lane >> 4) * H16_PLANE + (lane & 15) * 16;
 
     h16_dma_issue(hsm, in, Win, PB, bt, tile0, gstride, 0, g, lane, voff);
     // waits as builtins, not inline asm: the compiler's own wait insertion then knows the A loads and the

@@ -54,10 +54,7 @@ constexpr int WN_HALF = 576;                          // bytes of one channel ha
 constexpr int WN_PLANE = 2 * WN_HALF;
 constexpr int WN_STAGE = 32 * WN_PLANE;               // [xi 16][part 2] planes: 36,864 B
 constexpr size_t WN_RAW_OFF = 2 * (size_t)WN_STAGE;
-#ifndef WN_RING
-#define WN_RING 5                                     // raw buffers: LDS-DMA runs WN_RING - 2 steps ahead of use
-#endif
-static_assert(WN_RING == 3 || WN_RING == 5, "wait counts below are derived for rings of 3 and 5");
+constexpr int WN_RING = 5;                            // raw buffers: LDS-DMA runs WN_RING - 2 steps ahead of use
 constexpr size_t WN_BIAS_OFF = WN_RAW_OFF + WN_RING * (size_t)WN_RAW_BYTES;
 constexpr size_t WN_SMEM = WN_BIAS_OFF + NF * sizeof(float);
 static_assert(8 * 2 * WN_NT * 32 * 4 <= 2 * WN_STAGE, "P exchange fits the stages");
@@ -66,9 +63,6 @@ static_assert(WN_RAW_INS * 64 >= WN_IY * WN_IX * 4, "raw chunks");
 typedef float wn_f2 __attribute__((ext_vector_type(2)));
 typedef _Float16 wn_h2 __attribute__((ext_vector_type(2)));
 constexpr uint32_t WN_OOB = 0x80000000u;   // a voffset past num_records: the load returns 0
-#ifndef WN_VALU_PER_MFMA
-#define WN_VALU_PER_MFMA 5
-#endif
 
 __device__ __forceinline__ void wn_tile(const XpBatch &bt, int t, int &img, int &ty0, int &tx0)
 {
@@ -353,9 +347,9 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
         const float unscale_pass = unscale, s_pass = s;
         if (pass + 1 < npass) pass_src(pass + 1, src_nxt, rec_nxt);
         else { src_nxt = src_cur; rec_nxt = rec_cur; }
-        const float *src_nn = src_nxt;   // two passes ahead (WN_RING 5, step 3)
+        const float *src_nn = src_nxt;   // two passes ahead (the ring issues WN_RING steps ahead)
         uint32_t rec_nn = rec_nxt;
-        if (WN_RING > 4 && pass + 2 < npass) pass_src(pass + 2, src_nn, rec_nn);
+        if (pass + 2 < npass) pass_src(pass + 2, src_nn, rec_nn);
         floatx16 acc[2][2];
 #pragma unroll
         for (int p = 0; p < 2; p++)
@@ -396,7 +390,7 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
                 else issue(g + ahead, src_nn, rec_nn);
             }
             // stores of an epilogue between the wanted copy's issue (step g + 2 - WN_RING) and now
-            sync(more, pass > 0 && (WN_RING == 3 ? cb == 0 : cb < 3));
+            sync(more, pass > 0 && cb < 3);
         }
 
         // ---- epilogue: output transform, per M-tile ------------------------------------------

@@ -324,6 +324,47 @@ def test_tower_split_activation_layout(gpu):
     assert err <= 2e-6, err
 
 
+def test_tower_layer_api_mixed_layouts_vs_oracle(gpu, oracle):
+    """The layer-API instantiations no forward reaches, on a 4-layer tower (a first, a middle and a last layer) at
+    9 x 40: a middle layer that changes the activation layout (c-block in / [h][w][64] out and the reverse; every
+    split arithmetic), and a last layer that emits the hi / lo / norm planes from [h][w][64] or split activations.
+    Features against the fp64 oracle; emitted planes against sde_feature_split of the features, bit for bit."""
+    from scenedepthestimation_amd import mc_cnn, ops
+    L, H, W = 4, 9, 40
+    rng = np.random.default_rng(4009)
+    hw, hb = mc_cnn.layer_lists(mc_cnn.synthetic_weights(L, seed=L), L)
+    img = np.zeros((H + 2 * L, W + 2 * L), np.float32)
+    img[L:-L, L:-L] = rng.standard_normal((H, W)).astype(np.float32)
+    ref = oracle.tower_forward(img, hw, hb)
+    packed = dev(ops.pack_tower_weights(hw, hb))
+    # layout of layer 2's and layer 3's outputs; emit: the last layer writes the planes
+    chains = [(prec, l2, l3, False) for prec in ("bf16x6", "f16x3", "f16x3w", "f16x3m32")
+              for l2, l3 in (("cb", "hw"), ("hw", "cb"))]
+    chains += [("f16x3", "hw", "hw", True), ("f16x3", "split", "split", True)]
+    for prec, l2, l3, emit in chains:
+        x = dev(img)
+        words = torch.zeros(64, device="cuda")
+        ops.absmax(x, words[0:1])
+        lay = {1: "hw", 2: l2, 3: l3, 4: "hw"}      # lay[l]: layout of layer l's output
+        planes = ops.new_split(H, W, "cuda") if emit else None
+        for layer in range(2, L + 1):
+            shrink = 4 if layer == 2 else 2
+            y = torch.empty((x.shape[0] - shrink, x.shape[1] - shrink, 64), device="cuda")
+            ops.tower_layer(x, packed, L, layer, y, precision=prec, split=planes if layer == L else None,
+                            in_cblock=lay[layer - 1] == "cb", out_cblock=lay[layer] == "cb",
+                            in_absmax=words[layer - 2:layer - 1], out_absmax=words[layer - 1:layer] if layer < L else None,
+                            in_split=lay[layer - 1] == "split", out_split=lay[layer] == "split")
+            x = y
+        err = float(np.abs(host(x) - ref).max())
+        print(prec, l2, l3, emit, "vs fp64 oracle", err)
+        assert err < 1e-5, (prec, l2, l3, emit, err)
+        if emit:
+            again = ops.feature_split(x)
+            assert torch.equal(planes[0], again[0]) and torch.equal(planes[1], again[1]), (prec, l2)
+            true_n = np.sqrt((host(x).astype(np.float64) ** 2).sum(-1))
+            assert np.all(host(planes[2]) >= true_n) and np.all(host(planes[2]) <= true_n * 1.00001 + 1e-30)
+
+
 def test_tower_winograd_large_plane_takes_direct_kernel(gpu):
     """A 64->64 layer whose activation plane is >= 4 GiB (4100 x 4100 x 64 f32): the Winograd
     kernel's 32-bit descriptors cannot span it, so f16x3w must run the direct f16x3 kernel --

@@ -1,4 +1,5 @@
-"""Per-phase cycles of the tower's layer-3 launch from a probe build with H16_DIAG & 16384 (tools/variants/tower_h16_diag.h):
+"""Per-phase cycles of the tower's layer-3 launch from a probe build with the phase stamps of
+tools/variants/make_phase_header.py (the header it generates, substituted through -DSDE_H16_HEADER):
 every wave's lane 0 sums s_memtime deltas -- MFMA waves: c-block MFMAs, epilogue, barrier wait; stager waves: work,
 barrier wait -- and writes them to out[32 block + 4 wave ..].  Printed: median over workgroups per wave role, in
 kcycles per launch, and the MFMA floor (1728 MFMAs x 16 cycles per tile).

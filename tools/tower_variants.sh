@@ -1,7 +1,7 @@
 # Profiling builds of the persistent tower kernel -> tools/_var/libsde_t<name>.so, each built with
-# the -D options given as NAME=OPTS arguments (e.g. t2="-DTOWER_DIAG=2" r4="-DXP_RING_F16=4").
-# TOWER_DIAG bits: 1 stager HBM loads, 2 all stager work, 4 MFMAs, 8 MFMA-wave LDS reads,
-# 16 middle-layer output stores, 512 staged values replaced by constants (loads kept).  Run here (CPU), then time on the GPU with tools/tower_variants.py.
+# the compiler options given as NAME=OPTS arguments (e.g. split="-DSDE_SPLIT_ACT=1", or a generated probe header:
+# phase="-DSDE_H16_HEADER='\"$PWD/tools/_var/tower_h16_phase.h\"'", tools/variants/make_phase_header.py).
+# Run here (CPU), then time on the GPU with tools/tower_variants.py.
 set -e
 cd "$(dirname "$0")/.."
 rm -rf tools/_var; mkdir -p tools/_var
