@@ -152,12 +152,13 @@ __global__ __launch_bounds__(256) void cv64_kernel(const float *__restrict__ own
 }
 
 // ---------------------------------------------------------------------------
-// LDS-DMA helpers of the L/R volume sweep (cvlr3_kernel below).  Rounds 1-2 ran the sweep as
-// cvlr_row_kernel (register-staged, 2 workgroups per CU) and cvlr_dma_kernel (one 512-thread
-// workgroup per CU, LDS-DMA one dot loop ahead); both measured slower than cvlr3_kernel and were
-// removed in round 4 (DESIGN.md sec. 3.1 keeps their measurements).  The padded 272-B rows, the
-// 32-row DMA units (8.5 wave-instructions of 1 KiB; lane s loads chunk s % 17 of row s / 17, chunk
-// 16 the pad) and the raw barriers below are theirs.
+// LDS-DMA helpers of the L/R volume sweep (cvlr3_kernel below): feature rows go from global memory
+// straight into padded 272-B LDS rows, without passing through VGPRs.  A buffer descriptor per
+// feature row makes out-of-image rows load zeros (cd_desc); one wave-instruction moves 1 KiB
+// (cd_dma16); a unit is 32 padded rows = 8.5 instructions, lane s loading chunk s % 17 of row
+// s / 17, chunk 16 being the pad (cd_unit, c3_unit); cd_rsrc is the descriptor of the volume
+// stores, whose out-of-image rows are dropped by the range check; cd_barrier waits for the LDS
+// counter only, so DMA and stores stay in flight across the barrier.
 // ---------------------------------------------------------------------------
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -581,26 +582,11 @@ __global__ __launch_bounds__(256) void wta_hwd_kernel(const float *__restrict__ 
     }
 }
 
-__global__ __launch_bounds__(256) void argmin_merge_kernel(const float *__restrict__ mins,
-                                                           const int32_t *__restrict__ args, int nshards,
-                                                           int64_t npix, float *__restrict__ disp)
-{
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= npix) return;
-    float best = mins[p];
-    int arg = args[p];
-    for (int s = 1; s < nshards; s++) {
-        const float m = mins[(size_t)s * npix + p];
-        const int a = args[(size_t)s * npix + p];
-        if (m < best) { best = m; arg = a; }   // shards are ordered by d: ties keep the earlier one
-    }
-    disp[p] = (float)arg;
-}
-
-// Chunked certified CV + WTA (sde_cv_wta, D past one row sweep's LDS window): chunk k's exact first-minimum
+// Merge of per-range first minima: the disparity shards of sde_argmin_merge and the chunks of the chunked
+// certified CV + WTA (sde_cv_wta, D past one row sweep's LDS window).  Chunk k's exact first-minimum
 // (value, index) per pixel at mins / args + k * npix, chunks ordered by d; the pixel's first minimum over
-// all of them (strict <: a later chunk wins only with a smaller cost -- a sequential scan over d), written
-// to whichever outputs are requested.
+// all of them (strict <: a later chunk wins only with a smaller cost, ties keep the earlier one -- a
+// sequential scan over d), written to whichever outputs are requested.
 __global__ __launch_bounds__(256) void argmin_chunks_kernel(const float *__restrict__ mins,
                                                             const int32_t *__restrict__ args, int nchunks,
                                                             int64_t npix, float *__restrict__ disp,
@@ -992,14 +978,16 @@ SDE_EXPORT int sde_cost_volume(const float *fl, const float *fr, int H, int W, i
     return launch_status();
 }
 
-// certified-mode workspace: [counters 256 B][list 4*npix][planes 4 x 128*npix][norms 2 x 4*npix]; the fix-up
-// count of a call is the sum of the 64 counter words (one per disparity chunk, sde_cv_wta's chunked path)
+// certified-mode workspace: [counters 256 B][fix-up list 4*npix], then for sde_cv_wta the (min, arg) planes of
+// up to CERT_COUNTERS disparity chunks, 8 B per pixel each: 512*npix covers every K <= 64 (plus two rows of
+// 4*npix that earlier layouts used: callers size buffers by the byte counts, which therefore stay).  The fix-up
+// count of a call is the sum of the 64 counter words (one per chunk).
 constexpr int CERT_COUNTERS = 64;
-static int64_t cert_ws_bytes(int H, int W, bool with_planes)
+static int64_t cert_ws_bytes(int H, int W, bool with_chunks)
 {
     const int64_t npix = (int64_t)H * W;
     int64_t b = 256 + ((4 * npix + 255) / 256) * 256;
-    if (with_planes) b += 4 * 128 * npix + 2 * ((4 * npix + 255) / 256) * 256;
+    if (with_chunks) b += 4 * 128 * npix + 2 * ((4 * npix + 255) / 256) * 256;
     return b;
 }
 
@@ -1009,16 +997,10 @@ SDE_EXPORT int64_t sde_cv_wta_workspace_bytes(int H, int W)
     return cert_ws_bytes(H, W, true);
 }
 
-// chunked row sweep: [counter, list] then the chunks' (min, arg) planes; INT64_MAX when [d0, d1) does not split
-// into row-sweep-supported chunks (the chunk kernel path then runs)
-constexpr int ROW_CHUNK = 256;
-static int64_t row_chunk_layout(int H, int W, int d0, int d1)
+SDE_EXPORT int64_t sde_cv_wta_split_workspace_bytes(int H, int W)
 {
-    const int K = cdiv(d1 - d0, ROW_CHUNK);
-    if (K > CERT_COUNTERS) return INT64_MAX;
-    for (int k = 0; k < K; k++)
-        if (!row_cert_supported(d0 + k * ROW_CHUNK, std::min(d1, d0 + (k + 1) * ROW_CHUNK))) return INT64_MAX;
-    return cert_ws_bytes(H, W, false) + (int64_t)K * 8 * H * W;
+    if (H <= 0 || W <= 0) return -1;
+    return cert_ws_bytes(H, W, false);
 }
 
 SDE_EXPORT int sde_feature_split(const float *feat, int64_t npix, int C, uint16_t *hi, uint16_t *lo, float *norm,
@@ -1029,27 +1011,6 @@ SDE_EXPORT int sde_feature_split(const float *feat, int64_t npix, int C, uint16_
     return launch_status();
 }
 
-static int launch_cert(const float *fl, const float *fr, const uint16_t *lhi, const uint16_t *llo, const float *lnrm,
-                       const uint16_t *rhi, const uint16_t *rlo, const float *rnrm, int H, int W, int d0, int d1,
-                       float *disp, float *min_cost, int32_t *argmin, void *ws, hipStream_t st)
-{
-    unsigned *counter = reinterpret_cast<unsigned *>(ws);
-    int32_t *list = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(ws) + 256);
-    if (hipMemsetAsync(counter, 0, CERT_COUNTERS * sizeof(unsigned), st) != hipSuccess) return SDE_ERR_LAUNCH;
-    cv_wta_cert_kernel<<<cdiv(W, FX_NX) * H, 256, 0, st>>>(
-        fl, fr, reinterpret_cast<const uint4 *>(lhi), reinterpret_cast<const uint4 *>(llo), lnrm,
-        reinterpret_cast<const uint4 *>(rhi), reinterpret_cast<const uint4 *>(rlo), rnrm, H, W, d0, d1, min_cost,
-        argmin, disp, counter, list);
-    cv_wta_fixup_kernel<<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, counter, list, min_cost, argmin, disp);
-    return SDE_OK;
-}
-
-SDE_EXPORT int64_t sde_cv_wta_split_workspace_bytes(int H, int W)
-{
-    if (H <= 0 || W <= 0) return -1;
-    return cert_ws_bytes(H, W, false);
-}
-
 SDE_EXPORT int sde_cv_wta_split(const float *fl, const float *fr, const uint16_t *fl_hi, const uint16_t *fl_lo,
                                 const float *fl_norm, const uint16_t *fr_hi, const uint16_t *fr_lo,
                                 const float *fr_norm, int H, int W, int d0, int d1, float *disp, float *min_cost,
@@ -1058,11 +1019,21 @@ SDE_EXPORT int sde_cv_wta_split(const float *fl, const float *fr, const uint16_t
     if (!fl || !fr || !fl_hi || !fl_lo || !fl_norm || !fr_hi || !fr_lo || !fr_norm) return SDE_ERR_ARG;
     if (H <= 0 || W <= 0 || d0 < 0 || d1 <= d0 || (!disp && !min_cost && !argmin)) return SDE_ERR_ARG;
     if (!workspace || workspace_bytes < cert_ws_bytes(H, W, false)) return SDE_ERR_WORKSPACE;
-    const int s = launch_cert(fl, fr, fl_hi, fl_lo, fl_norm, fr_hi, fr_lo, fr_norm, H, W, d0, d1, disp, min_cost,
-                              argmin, workspace, as_stream(stream));
-    if (s != SDE_OK) return s;
+    hipStream_t st = as_stream(stream);
+    unsigned *counter = reinterpret_cast<unsigned *>(workspace);
+    int32_t *list = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + 256);
+    if (hipMemsetAsync(counter, 0, CERT_COUNTERS * sizeof(unsigned), st) != hipSuccess) return SDE_ERR_LAUNCH;
+    cv_wta_cert_kernel<<<cdiv(W, FX_NX) * H, 256, 0, st>>>(
+        fl, fr, reinterpret_cast<const uint4 *>(fl_hi), reinterpret_cast<const uint4 *>(fl_lo), fl_norm,
+        reinterpret_cast<const uint4 *>(fr_hi), reinterpret_cast<const uint4 *>(fr_lo), fr_norm, H, W, d0, d1,
+        min_cost, argmin, disp, counter, list);
+    cv_wta_fixup_kernel<<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, counter, list, min_cost, argmin, disp);
     return launch_status();
 }
+
+// disparities per chunk of the chunked row sweep.  A chunk spans 128 + 256 - 1 right pixels per superstrip, at
+// most 13 tiles of 32 whatever its first disparity: every chunk fits the row sweep's ring (row_cert_supported)
+constexpr int ROW_CHUNK = 256;
 
 SDE_EXPORT int sde_cv_wta(const float *fl, const float *fr, int H, int W, int C, int d0, int d1, float *disp,
                           float *min_cost, int32_t *argmin, int mode, void *workspace, int64_t workspace_bytes,
@@ -1072,55 +1043,45 @@ SDE_EXPORT int sde_cv_wta(const float *fl, const float *fr, int H, int W, int C,
     if (!disp && !min_cost && !argmin) return SDE_ERR_ARG;
     if (mode != SDE_CV_EXACT && mode != SDE_CV_CERTIFIED) return SDE_ERR_ARG;
     hipStream_t st = as_stream(stream);
-    if (C == 64 && mode == SDE_CV_CERTIFIED && row_cert_supported(d0, d1)) {
-        // row-sweep kernel straight from the fp32 features (cv_row.hip)
-        if (!workspace || workspace_bytes < sde_cv_wta_workspace_bytes(H, W)) return SDE_ERR_WORKSPACE;
-        unsigned *counter = reinterpret_cast<unsigned *>(workspace);
-        int32_t *list = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + 256);
-        if (hipMemsetAsync(counter, 0, CERT_COUNTERS * sizeof(unsigned), st) != hipSuccess) return SDE_ERR_LAUNCH;
-        launch_row_cert(fl, fr, H, W, d0, d1, min_cost, argmin, disp, counter, list, st);
-        cv_wta_fixup_kernel<<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, counter, list, min_cost, argmin, disp);
-    } else if (C == 64 && mode == SDE_CV_CERTIFIED && row_chunk_layout(H, W, d0, d1) <= sde_cv_wta_workspace_bytes(H, W)) {
-        // D past the row sweep's LDS window (e.g. BASELINE config 5, D = 512): ROW_CHUNK-disparity chunks, each
-        // through the row-sweep kernel + its exact fix-ups (the same outputs as the exact kernel on that
-        // range, as for the disparity shards of parallel.py), then the first minimum over the chunks in d order
+    auto exact64 = [&] {
+        dim3 grid(cdiv(W, CV_TX), H);
+        cv64_kernel<SDE_SIDE_LEFT, OUT_WTA><<<grid, 256, 0, st>>>(fl, fr, H, W, d0, d1, 0, -0.0f, nullptr, min_cost,
+                                                                   argmin, disp);
+    };
+    if (C == 64 && mode == SDE_CV_CERTIFIED) {
+        // The row-sweep kernel straight from the fp32 features (cv_row.hip) + the exact fix-ups of the pixels it
+        // lists: one sweep where [d0, d1) fits its ring, else ROW_CHUNK-disparity chunks (e.g. BASELINE config
+        // 5, D = 512) and the first minimum over the chunks in d order.  A range of more than CERT_COUNTERS
+        // chunks (D > 16384) takes the exact kernel: the certificate's contract is the exact kernel's outputs
+        // bit for bit, so only the speed differs, and the zeroed counters report no fix-ups.
         if (!workspace || workspace_bytes < sde_cv_wta_workspace_bytes(H, W)) return SDE_ERR_WORKSPACE;
         const int64_t npix = (int64_t)H * W;
         const int K = cdiv(d1 - d0, ROW_CHUNK);
         unsigned *counter = reinterpret_cast<unsigned *>(workspace);
         int32_t *list = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + 256);
-        float *cmin = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + cert_ws_bytes(H, W, false));
-        int32_t *carg = reinterpret_cast<int32_t *>(cmin + (size_t)K * npix);
-        // chunk k counts its fix-ups in counter word k (sde_cv_wta_fixups-style readers sum the words); the
-        // list is reused: chunk k's fix-ups run before chunk k + 1's sweep
         if (hipMemsetAsync(counter, 0, CERT_COUNTERS * sizeof(unsigned), st) != hipSuccess) return SDE_ERR_LAUNCH;
-        for (int k = 0; k < K; k++) {
-            const int a = d0 + k * ROW_CHUNK, b = std::min(d1, a + ROW_CHUNK);
-            launch_row_cert(fl, fr, H, W, a, b, cmin + (size_t)k * npix, carg + (size_t)k * npix, nullptr, counter + k,
-                            list, st, k > 0 ? cmin + (size_t)(k - 1) * npix : nullptr);
-            cv_wta_fixup_kernel<<<1024, 256, 0, st>>>(fl, fr, W, a, b, counter + k, list, cmin + (size_t)k * npix,
-                                                      carg + (size_t)k * npix, nullptr);
+        if (row_cert_supported(d0, d1)) {
+            launch_row_cert(fl, fr, H, W, d0, d1, min_cost, argmin, disp, counter, list, st);
+            cv_wta_fixup_kernel<<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, counter, list, min_cost, argmin, disp);
+        } else if (K <= CERT_COUNTERS) {
+            // each chunk's outputs are the exact kernel's on its range (as for the disparity shards of
+            // parallel.py).  Chunk k counts its fix-ups in counter word k; the list is reused: chunk k's fix-ups
+            // run before chunk k + 1's sweep
+            float *cmin = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + cert_ws_bytes(H, W, false));
+            int32_t *carg = reinterpret_cast<int32_t *>(cmin + (size_t)K * npix);
+            for (int k = 0; k < K; k++) {
+                const int a = d0 + k * ROW_CHUNK, b = std::min(d1, a + ROW_CHUNK);
+                float *mk = cmin + (size_t)k * npix;
+                int32_t *ak = carg + (size_t)k * npix;
+                launch_row_cert(fl, fr, H, W, a, b, mk, ak, nullptr, counter + k, list, st, k > 0 ? mk - npix : nullptr);
+                cv_wta_fixup_kernel<<<1024, 256, 0, st>>>(fl, fr, W, a, b, counter + k, list, mk, ak, nullptr);
+            }
+            argmin_chunks_kernel<<<cdiv(npix, 256), 256, 0, st>>>(cmin, carg, K, npix, disp, min_cost, argmin);
+        } else {
+            exact64();
         }
-        argmin_chunks_kernel<<<cdiv(npix, 256), 256, 0, st>>>(cmin, carg, K, npix, disp, min_cost, argmin);
-    } else if (C == 64 && mode == SDE_CV_CERTIFIED) {
-        if (!workspace || workspace_bytes < sde_cv_wta_workspace_bytes(H, W)) return SDE_ERR_WORKSPACE;
-        const int64_t npix = (int64_t)H * W;
-        char *base = reinterpret_cast<char *>(workspace) + cert_ws_bytes(H, W, false);
-        uint16_t *lhi = reinterpret_cast<uint16_t *>(base);
-        uint16_t *llo = lhi + 64 * npix;
-        uint16_t *rhi = llo + 64 * npix;
-        uint16_t *rlo = rhi + 64 * npix;
-        float *lnrm = reinterpret_cast<float *>(rlo + 64 * npix);
-        float *rnrm = lnrm + ((npix + 63) / 64) * 64;
-        feature_split_kernel<<<cdiv(npix * 16, 256), 256, 0, st>>>(fl, npix, lhi, llo, lnrm);
-        feature_split_kernel<<<cdiv(npix * 16, 256), 256, 0, st>>>(fr, npix, rhi, rlo, rnrm);
-        const int s = launch_cert(fl, fr, lhi, llo, lnrm, rhi, rlo, rnrm, H, W, d0, d1, disp, min_cost, argmin,
-                                  workspace, st);
-        if (s != SDE_OK) return s;
     } else if (C == 64) {
-        dim3 grid(cdiv(W, CV_TX), H);
-        cv64_kernel<SDE_SIDE_LEFT, OUT_WTA><<<grid, 256, 0, st>>>(fl, fr, H, W, d0, d1, 0, -0.0f, nullptr,
-                                                                   min_cost, argmin, disp);
+        exact64();
     } else {
         const int blocks = cdiv((int64_t)H * W, 256);
         cv_generic_kernel<OUT_WTA><<<blocks, 256, 0, st>>>(fl, fr, H, W, C, d0, d1, 0, SDE_SIDE_LEFT, -0.0f,
@@ -1153,6 +1114,7 @@ SDE_EXPORT int sde_argmin_merge(const float *mins, const int32_t *args, int nsha
                                 void *stream)
 {
     if (!mins || !args || !disp || nshards <= 0 || npix <= 0) return SDE_ERR_ARG;
-    argmin_merge_kernel<<<cdiv(npix, 256), 256, 0, as_stream(stream)>>>(mins, args, nshards, npix, disp);
+    argmin_chunks_kernel<<<cdiv(npix, 256), 256, 0, as_stream(stream)>>>(mins, args, nshards, npix, disp, nullptr,
+                                                                         nullptr);
     return launch_status();
 }

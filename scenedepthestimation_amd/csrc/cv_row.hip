@@ -14,30 +14,34 @@
 namespace sde {
 
 // ---------------------------------------------------------------------------
-// Row-sweep certified CV + WTA on fp32 features (cv_wta_row_kernel).
+// Mapping (cv_wta_row2_kernel).
 //
-// One 512-thread workgroup per image row walks the row in 256-pixel superstrips;
-// wave w owns the 32 left pixels [256k + 32w, +32) (one MFMA N-tile) and sweeps
-// every right tile of its disparity band itself, so a pixel's best / runner-up /
-// argmin never leave the wave (no cross-wave merge).  The right-feature window of
-// a superstrip (256 + D - 1 pixels, in 32-pixel tiles) lives in an LDS ring of
-// hi/lo bf16 planes; advancing one superstrip retires 8 tiles and admits 8, so
-// every right pixel is read from HBM once per row (the chunked kernel above
-// re-stages ~5x the window).  New tiles are loaded one superstrip ahead into
-// registers, then split into hi/lo (and their pixel norms and per-tile norm
-// maximum computed) by the threads that loaded them: no pre-split pass -- the
-// kernel's only HBM input is the two fp32 feature maps (the algorithmic minimum).
-// Left operands are prefetched one superstrip ahead and split in registers.
-// 12 MFMAs per 32x32 tile pair, then the certificate of cv_wta_cert_kernel: a
-// pixel whose best fast score beats the runner-up by more than 2 eps gets its
-// exact cost recomputed from the fp32 rows (L2-resident) when requested, the rest
-// go to the fix-up list.  Outputs are bit-identical to the exact kernel.  Tiles
-// left of the image are zero-filled, so an invalid voxel (x < d) scores exactly
-// +0 = -(-0.0), like the CPU path.
+// One 512-thread workgroup per image row walks the row in 128-pixel superstrips.  Its eight
+// waves have two roles:
+//   * waves 0-3 compute.  Wave g owns the 32 left pixels [128 k + 32 g, +32) of superstrip k (one
+//     MFMA N-tile): it splits them in registers from fp32 rows prefetched one superstrip ahead,
+//     sweeps every 32-pixel right tile of its disparity band itself (12 MFMAs per tile pair), so a
+//     pixel's best / runner-up / argmin never leave the wave (no cross-wave merge), and takes the
+//     certificate's decision per pixel.
+//   * waves 4-7 stage.  The right-feature window of a superstrip (128 + D - 1 pixels, in tiles)
+//     lives in an LDS ring of hi / lo fp16 planes; advancing one superstrip retires 4 tiles and
+//     admits 4, one per stager: its fp32 loads are issued a superstrip ahead, then split into the
+//     planes of the tile's ring slot, with the tile's max squared pixel norm and non-finite flag as
+//     whole-wave reductions (no atomics).  Every right pixel is read from HBM once per row, and
+//     the kernel's only HBM input is the two fp32 feature maps (no pre-split pass).
+// The ring holds the window plus 4 tiles (14 at D = 192, 112 KB): while the compute waves read
+// window k, the stagers write window k+1's four new tiles into the slots of the tiles superstrip
+// k-1 retired, so one barrier per superstrip orders both directions.  Tiles left of the image are
+// zero-filled, so an invalid voxel (x < d) scores exactly +0 = -(-0.0), like the CPU path.
+//
+// Per pixel, the certificate of cv_wta_cert_kernel (cost_volume.hip) with the bound below: if the
+// best fast score beats the runner-up by more than 2 eps, the fast argmax is the exact first
+// minimum, and its exact cost is recomputed from the fp32 rows (L2-resident) when requested; every
+// other pixel goes to the fix-up list.  Outputs are bit-identical to the exact kernel.
 // ---------------------------------------------------------------------------
-// Arithmetic of the fast scores (unlike the chunked kernels of cost_volume.hip, which use bf16
-// hi/lo): every operand is scaled by 2^RW_S (exact) and split into two fp16 parts, x*2^S = h + l
-// + r; the three partial products run on v_mfma_f32_32x32x16_f16, the eight small-term MFMAs
+// Arithmetic of the fast scores and their bound (the chunked kernels of cost_volume.hip use bf16
+// hi/lo instead): every operand is scaled by 2^RW_S (exact) and split into two fp16 parts, x*2^S =
+// h + l + r; the three partial products run on v_mfma_f32_32x32x16_f16, the eight small-term MFMAs
 // (l*h', h*l') of a tile before the four leading ones (h*h').  Bound per voxel (a = fl[x],
 // b = fr[x-d], Cauchy-Schwarz as in cost_volume.hip):
 //   split: |r| <= 2^-22 |x| 2^S (fp16 11-bit parts) and the dropped l*l' <= 2^-22 |ab| 2^2S
@@ -51,12 +55,13 @@ namespace sde {
 // 2^-25 per scaled element, 64 elements).  A pixel is certified only when its norm and the
 // window's largest norm are below 2^(15-S) - 1: no part can overflow fp16.
 constexpr int RW_S = 8;
-constexpr float RW_SCALE = 256.0f;                 // 2^RW_S
+constexpr float RW_SCALE = (float)(1 << RW_S);     // 2^RW_S
 constexpr float RW_K = 1.5e-5f;
 constexpr float RW_ABS = 9.3132257e-10f;           // 2^-30
 constexpr float RW_NMAX = 127.0f;                  // norm limit: 127 * 2^8 < 65504
 typedef _Float16 rw_f16x8 __attribute__((ext_vector_type(8)));
 
+// the split of one operand (the definition the bound and the CPU model of the tests refer to)
 __device__ __forceinline__ void rw_split(float x, _Float16 &h, _Float16 &l)
 {
     const float xs = x * RW_SCALE;
@@ -64,12 +69,19 @@ __device__ __forceinline__ void rw_split(float x, _Float16 &h, _Float16 &l)
     l = (_Float16)(xs - (float)h);
 }
 
-constexpr int RW_T = 32;           // pixels per tile (= one MFMA N-tile of left pixels)
-constexpr int RW_WAVES = 8;
-constexpr int RW_NX = RW_T * RW_WAVES;   // left pixels per superstrip (256)
-constexpr int RW_NEW = RW_NX / RW_T;     // tiles admitted per superstrip (8)
+// rw_split's parts of two scaled values x0, x1 (= x * RW_SCALE) at a time, packed (x0's part in the low half):
+// hi by one packed convert of the pair, lo = f16(x 2^S - hi) by v_fma_mix{lo,hi} from it (x 2^S - hi is exact
+// in fp32: the same bits)
+__device__ __forceinline__ void rw_split2(float x0, float x1, uint32_t &hi, uint32_t &lo)
+{
+    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+    const h2 hh = {(_Float16)x0, (_Float16)x1};
+    hi = __builtin_bit_cast(uint32_t, hh);
+    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=&v"(lo) : "v"(x0), "v"(hi));
+    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(x1), "v"(hi));
+}
 
-__device__ __forceinline__ int rw_slot(int T, int nt) { return ((T % nt) + nt) % nt; }
+constexpr int RW_T = 32;          // pixels per tile (= one MFMA N-tile of left pixels)
 
 // one 16-B unit (pixel u>>4, channels 4(u&15)..+3) of right tile T (zero outside the row)
 __device__ __forceinline__ float4 rw_load(const float *__restrict__ frrow, int W, int T, int u)
@@ -88,250 +100,11 @@ __device__ __forceinline__ float rw_dpp(float v)
 
 __device__ __forceinline__ bool rw_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 
-// split one unit into the ring slot's hi/lo planes; the pixel's 16 lanes reduce its squared norm
-// and the tile's 32 pixels (512 units = 8 waves x 64 lanes -> 4 pixels per wave) its maximum
-// (tmax) and whether any channel is non-finite (tbad).  Integer tests: this file is built with
-// relaxed NaN handling, which may not be trusted to keep float NaN tests.
-__device__ __forceinline__ void rw_store(uint4 *ring, unsigned *tmax, unsigned *tbad, int slot, int u, float4 v)
-{
-    const int px = u >> 4, q = u & 15;
-    _Float16 h0, h1, h2, h3, l0, l1, l2, l3;
-    rw_split(v.x, h0, l0); rw_split(v.y, h1, l1); rw_split(v.z, h2, l2); rw_split(v.w, h3, l3);
-    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-    const h4 hv = {h0, h1, h2, h3}, lv = {l0, l1, l2, l3};
-    char *base = reinterpret_cast<char *>(ring + slot * 512 + fx_slot(px, q >> 1)) + 8 * (q & 1);
-    *reinterpret_cast<uint2 *>(base) = __builtin_bit_cast(uint2, hv);
-    *reinterpret_cast<uint2 *>(base + 256 * 16) = __builtin_bit_cast(uint2, lv);
-    // the pixel's 16 lanes sum their squares by DPP (no LDS round trips): lane ^ 1, lane ^ 2, then the
-    // other quad of the 8 and the other 8 of the row by mirrors -- the partial sums are uniform
-    // within each quad / 8 by then, so every add is the xor-butterfly's add (same bits)
-    float ss = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    ss += rw_dpp<0xB1>(ss);     // quad_perm [1,0,3,2]
-    ss += rw_dpp<0x4E>(ss);     // quad_perm [2,3,0,1]
-    ss += rw_dpp<0x141>(ss);    // row_half_mirror
-    ss += rw_dpp<0x140>(ss);    // row_mirror
-    // squared norms are non-negative: their bit patterns order like unsigned integers; one LDS
-    // max per pixel (lane 16k) instead of a cross-row shuffle reduction
-    const bool bad = rw_nonfinite(v.x) || rw_nonfinite(v.y) || rw_nonfinite(v.z) || rw_nonfinite(v.w);
-    const uint64_t anybad = __ballot(bad);
-    if ((threadIdx.x & 15) == 0) atomicMax(&tmax[slot], __float_as_uint(ss));
-    if ((threadIdx.x & 63) == 0 && anybad) atomicOr(&tbad[slot], 1u);
-}
-
-template <bool WANT_MIN>
-__global__ __launch_bounds__(512) void cv_wta_row_kernel(const float *__restrict__ fl, const float *__restrict__ fr,
-                                                         int H, int W, int d0, int d1, int tlo0, int ntw,
-                                                         float *__restrict__ out_min, int32_t *__restrict__ out_arg,
-                                                         float *__restrict__ out_disp, unsigned *__restrict__ counter,
-                                                         int32_t *__restrict__ list)
-{
-    extern __shared__ __attribute__((aligned(16))) uint4 rsm[];
-    uint4 *ring = rsm;                                              // [ntw][2 planes][32 px][8 chunks]
-    unsigned *tmax = reinterpret_cast<unsigned *>(ring + ntw * 512); // [ntw] max squared pixel norm (f32 bits)
-    unsigned *tbad = tmax + ntw;                                    // [ntw] any non-finite channel
-
-    const int y = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: tile loop runs on SALU
-    const int j = lane & 31, h = lane >> 5;
-    const float *flrow = fl + (size_t)y * W * 64;
-    const float *frrow = fr + (size_t)y * W * 64;
-    const size_t rowpix = (size_t)y * W;
-    const int nss = (W + RW_NX - 1) / RW_NX;
-
-    // prologue: the first superstrip's window
-    for (int i = tid; i < ntw; i += 512) { tmax[i] = 0u; tbad[i] = 0u; }
-    __syncthreads();
-    {
-        // all loads in flight before the first store (a load -> store chain per tile would serialise
-        // ntw HBM latencies)
-        constexpr int MAXT = 18;
-        float4 pv[MAXT];
-#pragma unroll
-        for (int t = 0; t < MAXT; t++)
-            if (t < ntw) pv[t] = rw_load(frrow, W, tlo0 + t, tid);
-#pragma unroll
-        for (int t = 0; t < MAXT; t++)
-            if (t < ntw) rw_store(ring, tmax, tbad, rw_slot(tlo0 + t, ntw), tid, pv[t]);
-    }
-    // left operand (raw fp32: channels 16s+8h..+7 of pixel x), prefetched one superstrip ahead
-    float4 lraw[8];
-    auto load_left = [&](int kk) {
-        const int xx = kk * RW_NX + RW_T * wave + j;
-        const float4 *src = reinterpret_cast<const float4 *>(flrow) + (size_t)(xx < W ? xx : 0) * 16 + 2 * h;
-#pragma unroll
-        for (int s = 0; s < 4; s++) { lraw[2 * s] = src[4 * s]; lraw[2 * s + 1] = src[4 * s + 1]; }
-    };
-    load_left(0);
-    __syncthreads();
-
-    for (int k = 0; k < nss; k++) {
-        const int tlo = tlo0 + RW_NEW * k;
-        const bool more = k + 1 < nss;
-        // the next superstrip's 8 new tiles: loaded now, stored after this superstrip's reads
-        float4 nv[RW_NEW];
-#pragma unroll
-        for (int t = 0; t < RW_NEW; t++)
-            nv[t] = more ? rw_load(frrow, W, tlo + ntw + t, tid) : make_float4(0.f, 0.f, 0.f, 0.f);
-
-        const int xb = k * RW_NX + RW_T * wave;
-        const int x = xb + j;
-        const bool xok = x < W;
-        float best = -__builtin_inff(), second = -__builtin_inff();
-        int arg = -1;
-        float nl = 0.0f;
-        unsigned nmax2 = 0u, wbad = 0u;     // window: max squared norm (bits), any non-finite tile
-        bool lbad = false;
-        if (xb < W) {          // wave-uniform: waves past the row end only help with the ring
-            rw_f16x8 bh[4], bl[4];
-            float ssl = 0.0f;
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                const float4 a = lraw[2 * s], b = lraw[2 * s + 1];
-                const float v8[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    _Float16 hh, ll;
-                    rw_split(v8[e], hh, ll);
-                    bh[s][e] = hh;
-                    bl[s][e] = ll;
-                    ssl += v8[e] * v8[e];
-                    lbad |= rw_nonfinite(v8[e]);
-                }
-            }
-            ssl += __shfl_xor(ssl, 32, 64);
-            lbad |= __shfl_xor((int)lbad, 32, 64) != 0;
-            nl = sqrtf(ssl) * FX_NORM_UP;
-            if (more) load_left(k + 1);
-
-            float b1[4], b2[4];
-            int ag[4];
-#pragma unroll
-            for (int t = 0; t < 4; t++) { b1[t] = -__builtin_inff(); b2[t] = -__builtin_inff(); ag[t] = -1; }
-            // right tiles of this N-tile's band: d = x - xr in [d0, d1)
-            // right pixels xr in [xb - d1 + 1, xb + 31 - d0]: tiles floor(./32) (offset keeps it non-negative)
-            const int Ta = (xb - d1 + 1 + RW_T * 4096) / RW_T - 4096;
-            const int Tb = (xb + 31 - d0 + RW_T * 4096) / RW_T - 4096;
-            const int T0 = max(Ta, tlo), T1 = min(Tb, tlo + ntw - 1);
-            int slot = rw_slot(T0, ntw);                   // advanced incrementally (no division per tile)
-            for (int T = T0; T <= T1; T++, slot = (slot + 1 == ntw) ? 0 : slot + 1) {
-                const int dt = xb - RW_T * T;
-                const int dlo = dt - 31, dhi = dt + 31;
-                if (dhi < d0 || dlo >= d1) continue;     // wave-uniform
-                nmax2 = max(nmax2, tmax[slot]);
-                wbad |= tbad[slot];
-                const uint4 *tp = ring + slot * 512;
-                fx_floatx16 acc = {0};
-                rw_f16x8 ah[4], al[4];
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const int sl = fx_slot(j, 2 * s + h);
-                    ah[s] = __builtin_bit_cast(rw_f16x8, tp[sl]);
-                    al[s] = __builtin_bit_cast(rw_f16x8, tp[256 + sl]);
-                }
-                // the small terms first, then the leading products (the order the bound assumes)
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s], bh[s], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bl[s], acc, 0, 0, 0);
-                }
-#pragma unroll
-                for (int s = 0; s < 4; s++) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bh[s], acc, 0, 0, 0);
-                const int dl = dt + j - 4 * h;             // d of register r is dl - ((r&3) + 8(r>>2))
-                if (dlo >= d0 && dhi < d1) {
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int t = r & 3;
-                        const int d = dl - ((r & 3) + 8 * (r >> 2));
-                        const float sc = acc[r];
-                        const bool gt = sc > b1[t];
-                        ag[t] = gt ? d : ag[t];
-                        b2[t] = __builtin_amdgcn_fmed3f(b1[t], b2[t], sc);
-                        b1[t] = fmaxf(b1[t], sc);
-                    }
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int t = r & 3;
-                        const int d = dl - ((r & 3) + 8 * (r >> 2));
-                        const float sc = (d >= d0 && d < d1) ? acc[r] : -__builtin_inff();
-                        const bool gt = sc > b1[t];
-                        ag[t] = gt ? d : ag[t];
-                        b2[t] = __builtin_amdgcn_fmed3f(b1[t], b2[t], sc);
-                        b1[t] = fmaxf(b1[t], sc);
-                    }
-                }
-            }
-            best = b1[0]; second = b2[0]; arg = ag[0];
-#pragma unroll
-            for (int t = 1; t < 4; t++) fx_merge(best, arg, second, b1[t], ag[t], b2[t]);
-            {
-                const float bb = __shfl_xor(best, 32, 64), ss2 = __shfl_xor(second, 32, 64);
-                const int aa = __shfl_xor(arg, 32, 64);
-                fx_merge(best, arg, second, bb, aa, ss2);
-            }
-        }
-        __syncthreads();       // every wave is done reading the retiring tiles
-        if (more) {
-            for (int t = tid; t < RW_NEW; t += 512) {
-                tmax[rw_slot(tlo + ntw + t, ntw)] = 0u;
-                tbad[rw_slot(tlo + ntw + t, ntw)] = 0u;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int t = 0; t < RW_NEW; t++) rw_store(ring, tmax, tbad, rw_slot(tlo + ntw + t, ntw), tid, nv[t]);
-        }
-        // certificate and outputs (off the ring: overlaps the stores)
-        if (xb < W && h == 0 && xok) {
-            // scores are scaled by 2^2S (exact): compare against the scaled bound
-            const float nr = sqrtf(__uint_as_float(nmax2)) * FX_NORM_UP;
-            const float eps = (RW_K * nl * nr + RW_ABS * (nl + nr) + FX_ABS) * (RW_SCALE * RW_SCALE);
-            const size_t p = rowpix + x;
-            // certified only when every operand is finite and no fp16 part can overflow (then
-            // every score and eps are finite too)
-            // x < d0: no voxel of the band is inside the image -- every cost is the -0.0 fill, so the scan's
-            // first minimum is d0 whatever the features hold (the chunked path's later chunks: x < 256 k)
-            const bool none = x < d0;
-            if (none || (!lbad && !wbad && nl < RW_NMAX && nr < RW_NMAX && (best - second) > 2.0f * eps && arg >= 0)) {
-                if (none) arg = d0;
-                if (WANT_MIN) {
-                    float cost = -0.0f;
-                    if (x - arg >= 0)
-                        cost = dot64_exact_global(reinterpret_cast<const float4 *>(flrow + (size_t)x * 64),
-                                                  reinterpret_cast<const float4 *>(frrow + (size_t)(x - arg) * 64));
-                    out_min[p] = cost;
-                }
-                if (out_arg) out_arg[p] = arg;
-                if (out_disp) out_disp[p] = (float)arg;
-            } else {
-                // near-ties and non-finite operands: the IEEE fix-up kernel's exact scan
-                list[atomicAdd(counter, 1u)] = (int32_t)p;
-            }
-        }
-        __syncthreads();
-    }
-
-}
-
-// ---------------------------------------------------------------------------
-// Warp-specialised row sweep (cv_wta_row2_kernel) -- the default.
-//
-// In cv_wta_row_kernel all eight waves stage the window's new tiles (split, norms, ring writes)
-// and then all compute, in lock-step barrier phases around one 8-wave workgroup per CU (PMC:
-// waves parked 38 % of their cycles, MFMA pipe ~10 % busy).  Here the roles are split: waves
-// 0-3 compute (each owns 32 left pixels of a 128-pixel superstrip: left split, 12 MFMAs per
-// right tile of its band, the certificate -- the same arithmetic and bound as above), waves 4-7
-// stage: each admits one 32-pixel right tile per superstrip (fp32 loads issued a superstrip
-// ahead, split into the ring's hi / lo planes, the tile's max squared norm and non-finite flag
-// as whole-wave reductions, no atomics).  One barrier per superstrip: while the compute waves
-// read window k, the stagers write window k+1's four new tiles into the slots of the tiles
-// superstrip k-1 retired (ring = window + 4 tiles: 14 at D = 192, 112 KB).
-// ---------------------------------------------------------------------------
 constexpr int R2_NX = 128;                 // left pixels per superstrip (4 compute waves x 32)
 constexpr int R2_NEW = R2_NX / RW_T;       // tiles admitted per superstrip (4)
 constexpr int R2_LEAD = 2;                 // scores issued before the next tile's first MFMA (2..8 measured)
-// (the paired splits, the norm-based non-finite flags and the merge by permlane32 swaps below were each measured
-// against the plain form in round 5, DESIGN "Round 5 status")
+// (the paired splits, the norm-based non-finite flags and the merge by permlane32 swaps were each measured against
+// the plain form in round 5, DESIGN "Round 5 status")
 
 // one stager lane's 8 units (pixel u >> 4, channels 4 (u & 15) ..) of right tile T: unit u = lane + 64 i
 __device__ __forceinline__ void r2_load(const float *__restrict__ frrow, int W, int T, int lane, float4 (&v)[8])
@@ -350,21 +123,16 @@ __device__ __forceinline__ void r2_store(uint4 *ring, unsigned *tmax, unsigned *
     for (int i = 0; i < 8; i++) {
         const int u = lane + 64 * i, px = u >> 4, q = u & 15;
         char *base = reinterpret_cast<char *>(ring + slot * 512 + fx_slot(px, q >> 1)) + 8 * (q & 1);
-        // rw_split's parts as the compute waves' left split: hi of a scaled pair by one packed convert, lo by
-        // v_fma_mix{lo,hi} from it (x 2^S - hi exact in fp32: the same bits)
         const float xs[4] = {v[i].x * RW_SCALE, v[i].y * RW_SCALE, v[i].z * RW_SCALE, v[i].w * RW_SCALE};
-        typedef _Float16 h2 __attribute__((ext_vector_type(2)));
         uint32_t hw[2], lw[2];
 #pragma unroll
-        for (int e = 0; e < 2; e++) {
-            const h2 hh = {(_Float16)xs[2 * e], (_Float16)xs[2 * e + 1]};
-            hw[e] = __builtin_bit_cast(uint32_t, hh);
-            asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=&v"(lw[e]) : "v"(xs[2 * e]), "v"(hw[e]));
-            asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lw[e]) : "v"(xs[2 * e + 1]), "v"(hw[e]));
-        }
+        for (int e = 0; e < 2; e++) rw_split2(xs[2 * e], xs[2 * e + 1], hw[e], lw[e]);
         *reinterpret_cast<uint2 *>(base) = uint2{hw[0], hw[1]};
         *reinterpret_cast<uint2 *>(base + 256 * 16) = uint2{lw[0], lw[1]};
-        // the pixel's squared norm: its 16 lanes are one DPP row (same adds as rw_store)
+        // the pixel's squared norm: its 16 lanes are one DPP row and sum their squares without LDS
+        // round trips -- lane ^ 1, lane ^ 2, then the other quad of the 8 and the other 8 of the row
+        // by mirrors (the partial sums are uniform within each quad / 8 by then, so every add is
+        // the xor-butterfly's add: the same bits)
         float ss = v[i].x * v[i].x + v[i].y * v[i].y + v[i].z * v[i].z + v[i].w * v[i].w;
         ss += rw_dpp<0xB1>(ss);
         ss += rw_dpp<0x4E>(ss);
@@ -414,7 +182,9 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
         // ---------------- stagers ----------------
         const int sw = wave - 4;
         // window 0 (nw tiles, tile tlo0 + t by wave t % 4) and this wave's tile of window 1
-        // (nw <= 14: at most 4 prologue tiles per stager, all in flight together)
+        // (nw <= 14: at most 4 prologue tiles per stager, all loads in flight before the first store).
+        // The batch loop runs one trip (PB = 4); written flat, the compiler schedules the kernel differently,
+        // so it stays a loop until the schedule is re-measured.
         constexpr int PB = 4;                          // tiles per batch
         float4 nv[8];
 #pragma unroll
@@ -473,9 +243,7 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
         } else if (xb < W) {   // wave-uniform
             rw_f16x8 bh[4], bl[4];
             float ssl = 0.0f;
-            // rw_split's parts two values at a time: hi by one packed convert of the scaled pair, lo =
-            // f16(x 2^S - hi) by v_fma_mix{lo,hi} (x 2^S exact, x 2^S - hi exact in fp32: the same bits)
-            const float scl = RW_SCALE;
+            // the left split (the MFMAs' B fragments) and the pixel's squared norm
 #pragma unroll
             for (int s2 = 0; s2 < 4; s2++) {
                 const float4 a = lraw[2 * s2], b = lraw[2 * s2 + 1];
@@ -483,15 +251,7 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                 uint32_t hw[4], lw[4];
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {
-                    const float x0 = v8[e] * scl, x1 = v8[e + 1] * scl;
-                    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                    const h2 hh = {(_Float16)x0, (_Float16)x1};
-                    const uint32_t hv = __builtin_bit_cast(uint32_t, hh);
-                    uint32_t lv;
-                    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=&v"(lv) : "v"(x0), "v"(hv));
-                    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lv) : "v"(x1), "v"(hv));
-                    hw[e / 2] = hv;
-                    lw[e / 2] = lv;
+                    rw_split2(v8[e] * RW_SCALE, v8[e + 1] * RW_SCALE, hw[e / 2], lw[e / 2]);
                     ssl += v8[e] * v8[e];
                     ssl += v8[e + 1] * v8[e + 1];
                 }
@@ -523,10 +283,9 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                 // Same scores, same order of score updates: the same outputs.
                 // (every T in [T0, T1] is inside the band: Ta / Tb are its exact bounds)
                 const int n = T1 - T0 + 1;
-                // PD = 1: a tile's fragments are read at the start of the step before its MFMAs (PD = 2,
-                // a whole step earlier in two fragment buffers, spilled and measured slower, round 3)
-                constexpr int PD = 1;
-                rw_f16x8 fh[PD][4], fo[PD][4];
+                // Fragments are read one step ahead: a tile's hi / lo A fragments (fh, fo) at the start of
+                // the step that issues its MFMAs, the step that scores the tile before it.
+                rw_f16x8 fh[4], fo[4];
                 fx_floatx16 A[2];
                 auto nxt = [&](int sl2) { return sl2 + 1 == nt ? 0 : sl2 + 1; };
                 auto frag = [&](int sl2, rw_f16x8 (&ah)[4], rw_f16x8 (&al)[4]) {
@@ -563,14 +322,10 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                     b1[tt] = fmaxf(b1[tt], sc);
                 };
                 // scores of tile T (accumulators acc, ring slot sl2) interleaved with the MFMAs of the
-                // next tile (slot nsl; fragments fb, read now when PD = 1) into accn; PD = 2: the
-                // fragments of the tile after it (slot lsl) are read into lb first
-                auto step = [&](auto issue_c, auto load_c, int T, int sl2, const fx_floatx16 &acc, int nsl,
-                                fx_floatx16 &accn, rw_f16x8 (&fbh)[4], rw_f16x8 (&fbl)[4], int lsl,
-                                rw_f16x8 (&lbh)[4], rw_f16x8 (&lbl)[4]) {
-                    constexpr bool issue = decltype(issue_c)::value, load = decltype(load_c)::value;
-                    if (PD == 1 && issue) frag(nsl, fbh, fbl);
-                    if (PD == 2 && load) frag(lsl, lbh, lbl);
+                // next tile (slot nsl, its fragments read now) into accn; issue = false: the last tile, scores only
+                auto step = [&](auto issue_c, int T, int sl2, const fx_floatx16 &acc, int nsl, fx_floatx16 &accn) {
+                    constexpr bool issue = decltype(issue_c)::value;
+                    if (issue) frag(nsl, fh, fo);
                     nmax2 = max(nmax2, tmax[sl2]);
                     wbad |= tbad[sl2];
                     const int dt = xb - RW_T * T;
@@ -587,7 +342,7 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                         for (int r = 0; r < LD; r++) score1(acc, r, mode_c, dk);
 #pragma unroll
                         for (int m = 0; m < 12; m++) {
-                            if (issue) mfma(m, accn, fbh, fbl);
+                            if (issue) mfma(m, accn, fh, fo);
 #pragma unroll
                             for (int r = LD + (RS * m) / 12; r < LD + (RS * (m + 1)) / 12; r++)
                                 score1(acc, r, mode_c, dk);
@@ -607,30 +362,28 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                 if (n > 0) {
                     using yes = std::integral_constant<bool, true>;
                     using no = std::integral_constant<bool, false>;
-                    constexpr int B1 = PD - 1;                 // the buffer of odd tiles
                     int sa = slot;                              // slot of tile T0 + i2
-                    frag(sa, fh[0], fo[0]);
-                    if (PD == 2 && n > 1) frag(nxt(sa), fh[B1], fo[B1]);
+                    frag(sa, fh, fo);
 #pragma unroll
-                    for (int m = 0; m < 12; m++) mfma(m, A[0], fh[0], fo[0]);
+                    for (int m = 0; m < 12; m++) mfma(m, A[0], fh, fo);
                     int i2 = 0;
-                    for (; i2 + 3 < n; i2 += 2) {              // two tiles per trip: static buffers
-                        const int sb = nxt(sa), sc2 = nxt(sb), sd = nxt(sc2);
-                        step(yes{}, yes{}, T0 + i2, sa, A[0], sb, A[1], fh[B1], fo[B1], sc2, fh[0], fo[0]);
-                        step(yes{}, yes{}, T0 + i2 + 1, sb, A[1], sc2, A[0], fh[0], fo[0], sd, fh[B1], fo[B1]);
+                    for (; i2 + 3 < n; i2 += 2) {              // two tiles per trip: static accumulator sets
+                        const int sb = nxt(sa), sc2 = nxt(sb);
+                        step(yes{}, T0 + i2, sa, A[0], sb, A[1]);
+                        step(yes{}, T0 + i2 + 1, sb, A[1], sc2, A[0]);
                         sa = sc2;
                     }
                     // the last 1-3 tiles
                     const int sb = nxt(sa), sc2 = nxt(sb);
                     if (i2 + 2 < n) {
-                        step(yes{}, yes{}, T0 + i2, sa, A[0], sb, A[1], fh[B1], fo[B1], sc2, fh[0], fo[0]);
-                        step(yes{}, no{}, T0 + i2 + 1, sb, A[1], sc2, A[0], fh[0], fo[0], sc2, fh[B1], fo[B1]);
-                        step(no{}, no{}, T0 + i2 + 2, sc2, A[0], sc2, A[1], fh[B1], fo[B1], sc2, fh[0], fo[0]);
+                        step(yes{}, T0 + i2, sa, A[0], sb, A[1]);
+                        step(yes{}, T0 + i2 + 1, sb, A[1], sc2, A[0]);
+                        step(no{}, T0 + i2 + 2, sc2, A[0], sc2, A[1]);
                     } else if (i2 + 1 < n) {
-                        step(yes{}, no{}, T0 + i2, sa, A[0], sb, A[1], fh[B1], fo[B1], sb, fh[0], fo[0]);
-                        step(no{}, no{}, T0 + i2 + 1, sb, A[1], sb, A[0], fh[0], fo[0], sb, fh[B1], fo[B1]);
+                        step(yes{}, T0 + i2, sa, A[0], sb, A[1]);
+                        step(no{}, T0 + i2 + 1, sb, A[1], sb, A[0]);
                     } else {
-                        step(no{}, no{}, T0 + i2, sa, A[0], sa, A[1], fh[B1], fo[B1], sa, fh[0], fo[0]);
+                        step(no{}, T0 + i2, sa, A[0], sa, A[1]);
                     }
                 }
             }
@@ -682,10 +435,15 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
         // barrier per superstrip orders both directions
         __syncthreads();
         if (xb < W && h == 0 && xok) {
+            // scores are scaled by 2^2S (exact): compare against the scaled bound
             const float nr = sqrtf(__uint_as_float(nmax2)) * FX_NORM_UP;
             const float eps = (RW_K * nl * nr + RW_ABS * (nl + nr) + FX_ABS) * (RW_SCALE * RW_SCALE);
             const size_t p = rowpix + x;
-            const bool none = x < d0;   // as in cv_wta_row_kernel: every cost the -0.0 fill, first minimum d0
+            // x < d0: no voxel of the band is inside the image -- every cost is the -0.0 fill, so the scan's
+            // first minimum is d0 whatever the features hold
+            const bool none = x < d0;
+            // certified only when every operand is finite and no fp16 part can overflow (then every score
+            // and eps are finite too)
             const bool fin = !lbad && !wbad && nl < RW_NMAX && nr < RW_NMAX;
             if (!none && fin && WANT_MIN && prev_min && best + 2.0f * eps < -prev_min[p] * (RW_SCALE * RW_SCALE)) {
                 out_min[p] = __builtin_inff();
@@ -700,85 +458,51 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                 if (out_arg) out_arg[p] = arg;
                 if (out_disp) out_disp[p] = (float)arg;
             } else {
+                // near-ties and non-finite operands: the IEEE fix-up kernel's exact scan
                 list[atomicAdd(counter, 1u)] = (int32_t)p;
             }
         }
     }
 }
 
-// tiles spanned by a superstrip's window and the first one (superstrip 0), floor division
-static void row_window(int d0, int d1, int &tlo0, int &ntw)
+// Superstrip 0's window -- right pixels [-(d1 - 1), 127 - d0], first tile tlo0, nw tiles (floor division) --
+// and the ring that holds a window plus the R2_NEW tiles being admitted, with its per-tile words
+struct RowWindow {
+    int tlo0, nw, nt;
+    size_t smem;
+};
+
+static RowWindow row_window(int d0, int d1)
 {
     auto fdiv = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
-    tlo0 = fdiv(-(d1 - 1), RW_T);
-    const int thi0 = fdiv(RW_NX - 1 - d0, RW_T);
-    ntw = thi0 - tlo0 + 1;
+    RowWindow w;
+    w.tlo0 = fdiv(-(d1 - 1), RW_T);
+    w.nw = fdiv(R2_NX - 1 - d0, RW_T) - w.tlo0 + 1;
+    w.nt = w.nw + R2_NEW;
+    w.smem = (size_t)w.nt * 512 * 16 + (size_t)w.nt * 8;
+    return w;
 }
 
-static size_t row_smem(int ntw) { return (size_t)ntw * 512 * 16 + (size_t)ntw * 8; }
-
-// the warp-specialised kernel's window (128-pixel superstrips) and ring (window + 4 tiles)
-static void row2_window(int d0, int d1, int &tlo0, int &nw)
-{
-    auto fdiv = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
-    tlo0 = fdiv(-(d1 - 1), RW_T);
-    nw = fdiv(R2_NX - 1 - d0, RW_T) - tlo0 + 1;
-}
-
-// the ring and its per-tile words
-static size_t row2_smem(int nt) { return row_smem(nt); }
-
-static bool row2_supported(int d0, int d1)
-{
-    int tlo0 = 0, nw = 0;
-    row2_window(d0, d1, tlo0, nw);
-    return nw <= 14;                      // prologue: <= 4 tiles per stager; ring <= 18 tiles
-}
-
-bool row_cert_supported(int d0, int d1)
-{
-    int tlo0 = 0, ntw = 0;
-    row_window(d0, d1, tlo0, ntw);
-    return ntw <= 18 || row2_supported(d0, d1);
-}
+// the stagers' prologue holds at most 4 tiles each (nw <= 14 + the window-1 tile); ring <= 18 tiles, 144 KB
+bool row_cert_supported(int d0, int d1) { return row_window(d0, d1).nw <= 14; }
 
 void launch_row_cert(const float *fl, const float *fr, int H, int W, int d0, int d1, float *out_min, int32_t *out_arg,
                      float *out_disp, unsigned *counter, int32_t *list, hipStream_t st, const float *prev_min)
 {
     static std::atomic<uint64_t> attr{0};
-    constexpr int NT2 = 512;
     once_per_device(attr, [] {
-        (void)hipFuncSetAttribute((const void *)cv_wta_row_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  150 * 1024);
-        (void)hipFuncSetAttribute((const void *)cv_wta_row_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  150 * 1024);
         (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<false>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     });
-    if (row2_supported(d0, d1)) {
-        int tlo0 = 0, nw = 0;
-        row2_window(d0, d1, tlo0, nw);
-        const int nt = nw + R2_NEW;
-        if (out_min)
-            cv_wta_row2_kernel<true><<<H, NT2, row2_smem(nt), st>>>(fl, fr, H, W, d0, d1, tlo0, nw, nt,
-                                                                          out_min, out_arg, out_disp, counter, list,
-                                                                          prev_min);
-        else
-            cv_wta_row2_kernel<false><<<H, NT2, row2_smem(nt), st>>>(fl, fr, H, W, d0, d1, tlo0, nw, nt,
-                                                                           nullptr, out_arg, out_disp, counter, list,
-                                                                           nullptr);
-        return;
-    }
-    int tlo0 = 0, ntw = 0;
-    row_window(d0, d1, tlo0, ntw);
+    const RowWindow w = row_window(d0, d1);
     if (out_min)
-        cv_wta_row_kernel<true><<<H, 512, row_smem(ntw), st>>>(fl, fr, H, W, d0, d1, tlo0, ntw, out_min, out_arg,
-                                                               out_disp, counter, list);
+        cv_wta_row2_kernel<true><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, out_min, out_arg,
+                                                          out_disp, counter, list, prev_min);
     else
-        cv_wta_row_kernel<false><<<H, 512, row_smem(ntw), st>>>(fl, fr, H, W, d0, d1, tlo0, ntw, nullptr, out_arg,
-                                                                out_disp, counter, list);
+        cv_wta_row2_kernel<false><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, nullptr, out_arg,
+                                                           out_disp, counter, list, nullptr);
 }
 
 }  // namespace sde

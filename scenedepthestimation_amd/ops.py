@@ -97,10 +97,10 @@ def cv_wta(fl, fr, d0: int, d1: int, disp=None, min_cost=None, argmin=None, want
            workspace=None):
     """Fused cost volume + first-min over [d0, d1): WTA1(compute_cost_volume(fl, fr, d1)) when d0 = 0.
 
-    mode 'exact' (VALU, NumPy order for every voxel) or 'certified' (bf16x3 MFMA scores + error bound,
-    exact resolution of uncertified pixels): identical outputs.  workspace: uint8 tensor of
-    cv_wta_workspace_bytes(H, W) bytes (allocated if None); its first int32 holds the number of
-    pixels resolved exactly after the call."""
+    mode 'exact' (VALU, NumPy order for every voxel) or 'certified' (fp16 hi/lo MFMA scores of the row
+    sweep + error bound, exact resolution of uncertified pixels): identical outputs.  workspace: uint8
+    tensor of cv_wta_workspace_bytes(H, W) bytes (allocated if None); cv_wta_fixups(workspace) is the
+    number of pixels resolved exactly after the call."""
     pl, pr, H, W, C = _feat_pair(fl, fr)
     if "disp" in want and disp is None:
         disp = _empty((H, W), torch.float32, fl)

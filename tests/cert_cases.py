@@ -240,5 +240,5 @@ def check_shares(name, sh):
 
 
 def single_sweep(d0, d1):
-    """cv_row.hip's row2_supported: the range fits one row sweep's ring (else 256-disparity chunks)."""
+    """cv_row.hip's row_cert_supported: the range fits one row sweep's ring (else 256-disparity chunks)."""
     return (127 - d0) // 32 - (-(d1 - 1)) // 32 + 1 <= 14

@@ -855,6 +855,29 @@ def test_certified_adversarial_ties_and_nonfinite(gpu, oracle, W, D):
     assert np.array_equal(o["certified"][0][:3], ref)
 
 
+def test_certified_past_64_chunks_is_exact(gpu, oracle):
+    """A certified request over more than 64 chunks of 256 disparities (here 65, on 80 pixels) has no chunk
+    planes in the workspace and runs the exact kernel: the oracle's and the exact mode's bytes on every output,
+    and a fix-up count read from zeroed counters (the workspace arrives filled with 0xA5)."""
+    from scenedepthestimation_amd import ops
+    rng = np.random.default_rng(65)
+    H, W, d1 = 2, 40, 16400
+    fl = l2n(rng.standard_normal((H, W, 64)).astype(np.float32))
+    fr = l2n(rng.standard_normal((H, W, 64)).astype(np.float32))
+    fr[:, 20:32] = fr[:, 4:16]                # repeated texture -> exact cost ties
+    ws = torch.full((ops.cv_wta_workspace_bytes(H, W),), 0xA5, dtype=torch.uint8, device="cuda")
+    disp, mn, am = ops.cv_wta(dev(fl), dev(fr), 0, d1, mode="certified", want=("disp", "min", "argmin"), workspace=ws)
+    fix = ops.cv_wta_fixups(ws)
+    ed, em, ea = ops.cv_wta(dev(fl), dev(fr), 0, d1, mode="exact", want=("disp", "min", "argmin"))
+    omn, oam = oracle.cv_wta_shard(fl, fr, 0, d1)
+    assert host(mn).tobytes() == omn.tobytes()
+    assert host(am).tobytes() == oam.astype(np.int32).tobytes()
+    assert host(disp).tobytes() == oam.astype(np.float32).tobytes()
+    for got, ex in ((disp, ed), (mn, em), (am, ea)):
+        assert host(got).tobytes() == host(ex).tobytes()
+    assert 0 <= fix <= H * W
+
+
 def test_certified_fixup_rate_is_small_on_textured_pairs(gpu):
     """On a textured synthetic pair through the real tower, almost every pixel is certified."""
     from scenedepthestimation_amd import ops

@@ -11,6 +11,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bench import stereo_pair  # noqa: E402
+from scenedepthestimation_amd import ops  # noqa: E402
 from scenedepthestimation_amd.pipeline import StereoMatcher  # noqa: E402
 
 D = 192
@@ -42,6 +43,6 @@ for rnd in range(3):
     for s, m in ms.items():
         res.setdefault(s, []).append(timed(m.cost_wta))
 for (H, W), v in res.items():
-    fix = int(ms[(H, W)].cv_ws[:4].view(torch.int32).item())
+    fix = ops.cv_wta_fixups(ms[(H, W)].cv_ws)
     print(f"H={H:5d} W={W:5d}  rows/CU {H / 256:5.2f}  {statistics.median(v):8.1f} us  "
           f"({' '.join(f'{t:.1f}' for t in v)})  fix-ups {fix}", flush=True)
