@@ -1,5 +1,5 @@
 // tower_h16.h -- the MC-CNN tower's 64 -> 64 layers (3..L; mc_cnn_brunch.py:31-48, conv :70-92) as
-// a direct 3x3 implicit GEMM on v_mfma_f32_16x16x32_f16 (included by tower.hip; f16x3 arithmetic).
+// a direct 3x3 implicit GEMM on v_mfma_f32_16x16x32_f16 (instantiated in tower_h16.hip; f16x3 arithmetic).
 //
 // Same arithmetic contract as conv64_x6p_kernel's F16 path: weights scaled by 2^tau on the host,
 // activations by 2^sigma (from the input's bound word) on the device, each split exactly into two
@@ -29,6 +29,9 @@
 //   per (row, half, quarter); the c-block-major output [cblk16][h][w][16] is written as 1 KB
 //   runs; the last layer L2-normalises over the 4 lanes x 4 quarters that hold a pixel.
 #pragma once
+#ifndef SDE_TOWER_H16_H   // also a named guard: a probe copy (SDE_H16_HEADER) must empty tower_h16q.h's include of this file
+#define SDE_TOWER_H16_H
+#include "tower_common.h"
 
 namespace sde {
 
@@ -47,8 +50,6 @@ static_assert(H16_SMEM <= 163840, "LDS");
 constexpr size_t H16_WIN_OFF = H16_SMEM;
 constexpr size_t H16_SMEM_FIRST = H16_WIN_OFF + XP_WIN * sizeof(float);   // 162,880 B
 static_assert(H16_SMEM_FIRST <= 163840, "LDS (layer 2)");
-// Timing-only builds substitute a generated probe copy of this header (in-kernel clock stamps:
-// tools/variants/make_phase_header.py; tools/build_file_variant.sh -DSDE_H16_HEADER=...).
 // Cache-policy bits of the stagers' activation loads: 1 (sc0) streams each activation past the CU's L1,
 // which leaves the L1 to the A fragments all four MFMA waves re-read every tap.  Timing builds showed the
 // MFMA waves waiting on those fragments (a probe build with the same loads issued but not consumed runs 149 us
@@ -349,17 +350,17 @@ struct H16B {
     f16x8 hi, lo;
 };
 
-// B fragment of step b = (half-tap b >> 3, row (b >> 1) & 3, pixel half b & 1); sb = the stage at the
-// lane's base.
-__device__ __forceinline__ H16B h16_bfrag(const char *sb, int b)
+// B fragment of (tap, row r, pixel half ph); sb = the stage at the lane's base.
+__device__ __forceinline__ H16B h16_bfrag_at(const char *sb, int tap, int r, int ph)
 {
-    const int tap = b >> 4, r = (b >> 1) & 3, ph = b & 1;
     const int off = ((r + tap / 3) * XP_IX + 16 * ph + tap % 3) * 16;
     H16B f;
     f.hi = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(sb + off));
     f.lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(sb + 4 * H16_PLANE + off));
     return f;
 }
+// ... of step b = (half-tap b >> 3, row (b >> 1) & 3, pixel half b & 1)
+__device__ __forceinline__ H16B h16_bfrag(const char *sb, int b) { return h16_bfrag_at(sb, b >> 4, (b >> 1) & 3, b & 1); }
 
 __device__ __forceinline__ floatx4 mfma16(f16x8 a, f16x8 b, floatx4 c)
 {
@@ -407,15 +408,7 @@ __device__ __forceinline__ void h16_cblock(floatx4 (&acc)[32], H16A (&abuf)[NA],
 // PH) % 4] for half-tap h; 18 half-taps per c-block, so the two c-blocks of a tile run in phases 0 and 2):
 // tap s requests tap s + 1 into the slots tap s - 1 left; on exit abuf holds A(ncb, tap 0) at phase PH + 2.
 // Every accumulator takes the same MFMAs in the same order as h16_cblock: the same bits.
-__device__ __forceinline__ H16B h16_bfrag12(const char *sb, int b)
-{
-    const int tap = b >> 3, r = (b >> 1) & 3, ph = b & 1;
-    const int off = ((r + tap / 3) * XP_IX + 16 * ph + tap % 3) * 16;
-    H16B f;
-    f.hi = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(sb + off));
-    f.lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(sb + 4 * H16_PLANE + off));
-    return f;
-}
+__device__ __forceinline__ H16B h16_bfrag12(const char *sb, int b) { return h16_bfrag_at(sb, b >> 3, (b >> 1) & 3, b & 1); }
 
 // BRD: depth of the B ring (fragments read BRD - 1 (row, half) steps ahead).  Depth 3 (two steps, 24 MFMAs
 // ahead) takes the MFMA waves' c-block loop from 280 to 249-274 kcycles per launch against the 232-kcycle MFMA floor
@@ -523,7 +516,7 @@ __device__ __forceinline__ void h16_epilogue(const floatx4 (&acc)[32], int lane,
                     if (OSPL) {
                         u32x2 hw2, lw2;
                         xp_split16s(o, hw2, lw2);
-                        const u32x4 v4 = xp_pair_parts<false>(hw2, lw2);
+                        const u32x4 v4 = xp_pair_parts(hw2, lw2);
                         pin[k] = v4;
                         if (rok) {
                             if (xok) {
@@ -745,3 +738,5 @@ __global__ __launch_bounds__(512) void conv64_h16_kernel(const float *__restrict
 }
 
 }  // namespace sde
+
+#endif  // SDE_TOWER_H16_H

@@ -1,6 +1,6 @@
 // tower_h16q.h -- the MC-CNN tower's middle 64 -> 64 layers (3..L-1; mc_cnn_brunch.py:31-48, conv :70-92) on
 // split activations (SDE_TOWER_IN_SPLIT | SDE_TOWER_OUT_SPLIT), as a 4-wave kernel whose weights stay in
-// registers (included by tower.hip after tower_h16.h; f16x3 arithmetic, v_mfma_f32_16x16x32_f16).
+// registers (instantiated in tower_h16.hip; f16x3 arithmetic, v_mfma_f32_16x16x32_f16).
 //
 // Same arithmetic contract and tiles as conv64_h16_kernel (16 x 32 output tiles, 2 c-blocks of 32 input
 // channels, the stage's 8 fp16 planes, lo*hi + hi*lo + hi*hi per product, small terms first), different
@@ -24,6 +24,7 @@
 //   pairs swap halves, one 16-B store per lane per (row, half)), every store issued (rows / columns past
 //   the output take the out-of-range offset), so the wait before the barrier can count them.
 #pragma once
+#include "tower_h16.h"
 
 namespace sde {
 
@@ -93,15 +94,7 @@ __device__ __forceinline__ void h16q_load_a(H16QA &a, const float *__restrict__ 
 
 // B fragment of step b = (tap, row r, half ph); sb = the stage at the lane's base (plane lane >> 4, pixel
 // lane & 15 of the wave's first row)
-__device__ __forceinline__ H16B h16q_bfrag(const char *sb, int b)
-{
-    const int tap = b / (2 * H16Q_NR), r = (b >> 1) % H16Q_NR, ph = b & 1;
-    const int off = ((r + tap / 3) * XP_IX + 16 * ph + tap % 3) * 16;
-    H16B f;
-    f.hi = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(sb + off));
-    f.lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(sb + 4 * H16_PLANE + off));
-    return f;
-}
+__device__ __forceinline__ H16B h16q_bfrag(const char *sb, int b) { return h16_bfrag_at(sb, b / (2 * H16Q_NR), (b >> 1) % H16Q_NR, b & 1); }
 
 constexpr int H16Q_RD = 4;   // B ring depth
 
@@ -174,7 +167,7 @@ __device__ __forceinline__ void h16q_epilogue(const floatx4 (&acc)[32], int lane
                 u32x2 hw2, lw2;
                 xp_split16s(o, hw2, lw2);
                 const int k = r * 2 + ph;
-                pin[k] = xp_pair_parts<false>(hw2, lw2);
+                pin[k] = xp_pair_parts(hw2, lw2);
                 __builtin_amdgcn_raw_buffer_store_b128(pin[k], rs, ok ? lane_pl + (uint32_t)x * 16u : XP_OOB, so, 0);
                 if (k >= XP_PIN - 1) asm volatile("" ::"v"(pin[k - (XP_PIN - 1)]));
             }

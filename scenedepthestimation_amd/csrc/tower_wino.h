@@ -1,5 +1,5 @@
-// tower_wino.h -- Winograd F(2x2, 3x3) for the MC-CNN tower's 64 -> 64 layers (included by
-// tower.hip; f16x3 arithmetic).  Replaces, for layers 3..L (mc_cnn_brunch.py:31-48, conv
+// tower_wino.h -- Winograd F(2x2, 3x3) for the MC-CNN tower's 64 -> 64 layers (instantiated in
+// tower_wino.hip; f16x3 arithmetic).  Replaces, for layers 3..L (mc_cnn_brunch.py:31-48, conv
 // :70-92), the direct conv64_x6p_kernel: per 2x2 output block the 3x3 correlation of a 4x4
 // input patch d with the weights g is
 //     Y = A^T [ sum_cin (G g G^T) .* (B^T d B) ] A,
@@ -41,10 +41,10 @@
 // the direct kernel, and the output transform adds <= 6 fp32 terms: fp32-level (measured
 // against the fp64 restatement in the tests: below the direct kernel's error).
 #pragma once
+#include "tower_common.h"
 
 namespace sde {
 
-constexpr int WN_TY = 8, WN_TX = 16;                  // outputs per pass
 constexpr int WN_TTY = 4, WN_TTX = 8;                 // Winograd tiles per pass
 constexpr int WN_NT = WN_TTY * WN_TTX;                // 32 tiles (one MFMA N-tile)
 constexpr int WN_IY = WN_TY + 2, WN_IX = WN_TX + 2;   // input region 10 x 18
@@ -62,7 +62,6 @@ static_assert(WN_RAW_INS * 64 >= WN_IY * WN_IX * 4, "raw chunks");
 
 typedef float wn_f2 __attribute__((ext_vector_type(2)));
 typedef _Float16 wn_h2 __attribute__((ext_vector_type(2)));
-constexpr uint32_t WN_OOB = 0x80000000u;   // a voffset past num_records: the load returns 0
 
 __device__ __forceinline__ void wn_tile(const XpBatch &bt, int t, int &img, int &ty0, int &tx0)
 {
@@ -75,22 +74,9 @@ __device__ __forceinline__ void wn_tile(const XpBatch &bt, int t, int &img, int 
 // 2^sigma for V of a tile: |V| <= 4 |input| (four-term sums), bound word * 4 in [2^14, 2^15)
 __device__ __forceinline__ void wn_scales(const float *__restrict__ in_amax, float tau_inv, float &s, float &unscale)
 {
-    const float bound = 4.0f * *in_amax;
-    int e = 0;
-    if (bound >= 1.17549435e-38f && bound <= 3.40282347e38f) e = (int)((__float_as_uint(bound) >> 23) & 255u) - 127;
-    const int sigma = min(max(14 - e, -100), 100);
+    const int sigma = xp_sigma(4.0f * *in_amax);
     s = ldexpf(1.0f, sigma);
     unscale = ldexpf(tau_inv, -sigma);
-}
-
-// Buffer descriptor on a wave-uniform base with num_records bytes (range-checked accesses).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wn_rsrc(const void *base, uint32_t bytes)
-{
-    const uintptr_t b = (uintptr_t)base;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)hi << 32) | lo), 0,
-                                             (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 
 // x * s split into two fp16 parts (x * s = h + l + r, |r| <= 2^-22 |x s|), a channel pair packed
@@ -145,13 +131,13 @@ __device__ __forceinline__ void wn_read_p23(uint32_t pa, wn_f4 (&pr)[4])
 }
 
 // LDS-DMA chunk of wave-instruction ins, lane ln: pixel (chunk >> 2) of the 10 x 18 region,
-// channels 4 (chunk & 3).. -- its byte offset from the region's origin (WN_OOB past the region)
+// channels 4 (chunk & 3).. -- its byte offset from the region's origin (XP_OOB past the region)
 template <bool IN_CB>
 __device__ __forceinline__ uint32_t wn_loff(int ins, int ln, int Win)
 {
     const int ch = ins * 64 + ln, px = ch >> 2, q = ch & 3;
     const int iy = px / WN_IX, ix = px - iy * WN_IX;
-    return px < WN_IY * WN_IX ? (uint32_t)(iy * Win + ix) * (IN_CB ? 64u : 256u) + 16u * q : WN_OOB;
+    return px < WN_IY * WN_IX ? (uint32_t)(iy * Win + ix) * (IN_CB ? 64u : 256u) + 16u * q : XP_OOB;
 }
 
 struct WnA {
@@ -182,7 +168,7 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
     // resident U fragments: positions 2w + p, M-tile m, c-block cb, parts h / l
     WnA u[2][2][4];
     {
-        const __amdgpu_buffer_rsrc_t ru = wn_rsrc(wkblob + LK_WINO, (uint32_t)LK_WU * 2u);
+        const __amdgpu_buffer_rsrc_t ru = xp_rsrc_n(wkblob + LK_WINO, (uint32_t)LK_WU * 2u);
 #pragma unroll
         for (int p = 0; p < 2; p++)
 #pragma unroll
@@ -215,8 +201,8 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
     };
     auto issue = [&](int g, const float *base, uint32_t bytes) {
         const int cb = g & 3;
-        const __amdgpu_buffer_rsrc_t rs = IN_CB ? wn_rsrc(base + (size_t)cb * Hin * Win * 16, bytes)
-                                                : wn_rsrc(base + cb * 16, bytes - 64u * cb);
+        const __amdgpu_buffer_rsrc_t rs = IN_CB ? xp_rsrc_n(base + (size_t)cb * Hin * Win * 16, bytes)
+                                                : xp_rsrc_n(base + cb * 16, bytes - 64u * cb);
         char *rb = wsm + WN_RAW_OFF + (size_t)(g % WN_RING) * WN_RAW_BYTES;
         int ln = lane;
         asm volatile("" : "+v"(ln));
@@ -407,7 +393,7 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
         const int fq = tid_e & 7, fj = (tid_e >> 3) & 1, ft = tid_e >> 4;
         const int oy = ty0 + 2 * (ft >> 3), ox = tx0 + 2 * (ft & 7) + fj;
         const __amdgpu_buffer_rsrc_t orsrc =
-            wn_rsrc(LAST ? out + (size_t)img * bt.pix_stride * NF : out + img * bt.out_stride, (uint32_t)Hout * Wout * 256u);
+            xp_rsrc_n(LAST ? out + (size_t)img * bt.pix_stride * NF : out + img * bt.out_stride, (uint32_t)Hout * Wout * 256u);
         float4 ylast[2][2];
         uint32_t amax = 0u;
 #pragma unroll
@@ -474,7 +460,7 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
                 const uint32_t off = OUT_CB ? (((uint32_t)(c0 >> 4) * Hout + y) * Wout + ox) * 64u + 4u * (c0 & 15)
                                             : ((uint32_t)y * Wout + ox) * 256u + 4u * c0;
                 const u32x4 od = __builtin_bit_cast(u32x4, o);
-                __builtin_amdgcn_raw_buffer_store_b128(od, orsrc, ok ? off : WN_OOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(od, orsrc, ok ? off : XP_OOB, 0, 0);
                 // the store's data registers stay untouched for >= 9 wait states ("store-data
                 // overwrite"; _isa_lint.MFMA_STORE_DATA_WINDOW)
                 asm volatile("s_nop 7\n\ts_nop 1" ::"v"(od));
@@ -493,7 +479,7 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
                 ss += __shfl_xor(ss, 4, 64);
                 const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
                 const int y = oy + i;
-                const uint32_t off = y < Hout && ox < Wout ? ((uint32_t)y * Wout + ox) * 256u + 16u * fq : WN_OOB;
+                const uint32_t off = y < Hout && ox < Wout ? ((uint32_t)y * Wout + ox) * 256u + 16u * fq : XP_OOB;
                 const u32x4 oa = __builtin_bit_cast(u32x4, make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv));
                 const u32x4 ob = __builtin_bit_cast(u32x4, make_float4(b.x * inv, b.y * inv, b.z * inv, b.w * inv));
                 __builtin_amdgcn_raw_buffer_store_b128(oa, orsrc, off, 0, 0);

@@ -22,7 +22,7 @@ import torch
 from . import mc_cnn, ops
 
 
-AMAX_WORDS = 64   # f16x3 bound words per image in the tower workspace (TOWER_AMAX_BYTES / 4)
+AMAX_WORDS = ops.AMAX_ROW_WORDS   # f16x3 bound words per image in the tower workspace (TOWER_AMAX_BYTES / 4)
 SPLIT_MAX_PIX = 1 << 24   # split activations: fewer input pixels per plane than this (tower.hip SPLIT_MAX_PIX)
 # Placement draws of the four SGM volumes (StereoMatcher._place_sgm_volumes): volumes of [MIN, MAX] voxels are
 # placed by up to this many allocate-and-time draws (larger ones would hold three 4-volume sets of > 6 GB each).

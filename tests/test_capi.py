@@ -140,6 +140,20 @@ def test_argument_validation_without_gpu():
     assert scaled(3, 8 | 64 | 128 | 2) == ERR           # IN_SPLIT with IN_CBLOCK
     assert scaled(3, 8 | 64 | 128 | 32) == ERR          # with the 32x32x16 kernel
     assert scaled(3, 8 | 64 | 128, L=33) == ERR         # the scale word needs <= 32 layers
+    # sde_tower_layer_batch shares these checks: the same refusals through it (one image: no stride rules)
+    batched = lambda layer, flags, L=5, h=8, w=8, out_amax=1: lib.sde_tower_layer_batch(
+        1, 1, 0, h, w, 1, L, 64, layer, 1, 0, flags, 1, out_amax, 64, N)
+    assert batched(1, 0) == ERR                          # layer 1
+    assert batched(3, 8, out_amax=N) == ERR              # no out bound
+    assert batched(3, 9) == ERR                          # two precisions
+    assert batched(3, 64) == ERR
+    assert batched(2, 8 | 64) == ERR
+    assert batched(5, 8 | 128) == ERR
+    assert batched(3, 8 | 64) == ERR and batched(3, 8 | 128) == ERR
+    assert batched(3, 8 | 64 | 128 | 2) == ERR
+    assert batched(3, 8 | 64 | 128 | 32) == ERR
+    assert batched(3, 8 | 64 | 128, L=33) == ERR
+    assert batched(3, 8 | 64 | 128, h=4098, w=4096) == ERR   # the split input plane's pixel limit (below)
     # split activations over a batch: image i's scale word (bound word + 32) must not reach image i + 1's row
     batch = lambda stride: lib.sde_tower_layer_batch(1, 2, 8 * 8 * 64, 8, 8, 1, 5, 64, 3, 1, 6 * 6 * 64,
                                                      8 | 64 | 128, 1, 1, stride, N)

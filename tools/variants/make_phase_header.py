@@ -2,7 +2,7 @@
 round-6 phase probe, applied to the current product code by exact-text anchors so the probe never drifts from
 it: a moved anchor is an assertion here, not a stale copy).  Every wave's lane 0 writes 4 floats to out[32 blockIdx.x + 4 wave ..] at the end:
 MFMA waves (c-block loop, epilogue, barrier), stagers (work, barrier).  Timing-only: wrong outputs in tile-0 rows.
-usage: python tools/variants/make_phase_header.py && bash tools/build_file_variant.sh tower.hip phase \\
+usage: python tools/variants/make_phase_header.py && bash tools/build_file_variant.sh tower_h16.hip phase \\
          -DSDE_H16_HEADER='"'$PWD/tools/_var/tower_h16_phase.h'"'   then python tools/tower_phase.py tools/_var/libsde_phase.so"""
 import os
 
