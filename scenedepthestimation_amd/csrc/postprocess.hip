@@ -1,0 +1,206 @@
+// postprocess.hip -- the GPU path's disparity post-processing (gfx950): left-right check, LRC fill, 5x5 median.
+//
+// Replaces (process_functional.py):
+//   is_error_match_kernel / LRC_kernel :977-1088
+//   Median_Filter_kernel               :840-879
+#include "sde_common.h"
+
+namespace sde {
+
+__device__ __forceinline__ int u8cast(double v) { return (int)((long long)v & 255); }
+
+__global__ __launch_bounds__(256) void lr_check_kernel(const float *__restrict__ dl, const float *__restrict__ dr,
+                                                       int H, int W, uint8_t *__restrict__ lrcl,
+                                                       uint8_t *__restrict__ lrcr)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (int64_t)H * W) return;
+    const int y = (int)(p / W), x = (int)(p % W);
+    const double ld = dl[p];
+    const double rd = (double)x - ld;
+    if (rd >= 0) {
+        const double mn = ld - (double)dr[(size_t)y * W + u8cast(rd)];
+        lrcl[p] = (mn > 1 || mn < -1) ? 1 : 0;
+    }
+    const double rd2 = dr[p];
+    const double ld2 = (double)x + rd2;
+    if (ld2 < W) {
+        const double mn = rd2 - (double)dl[(size_t)y * W + u8cast(ld2)];
+        lrcr[p] = (mn > 1 || mn < -1) ? 1 : 0;
+    }
+}
+
+// LRC_kernel (:1003-1088): every flagged pixel takes the mean of the nearest unflagged
+// pixel above, below, to the right and to the left (each only if it exists), summed in
+// that order in float64.  The reference walks each direction pixel by pixel, which is
+// quadratic in the length of a flagged run; here linear scans find the same four
+// pixels.  Pass 1 (wave per column): nearest unflagged row above / below of every
+// flagged pixel, parked in the output as two 16-bit row indices (0xFFFF = none).
+// Pass 2 (wave per row): nearest unflagged column to the left (sweep left -> right) and
+// to the right (sweep right -> left) by wave-wide max-scans over 64-pixel chunks; the
+// right sweep, which runs second, has all four neighbours and writes the result.
+constexpr uint32_t LRC_NONE = 0xFFFFu;
+
+// inclusive max-scan over the 64 lanes
+__device__ __forceinline__ int wave_max_scan(int v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o, 64);
+        if (lane >= o) v = v > t ? v : t;
+    }
+    return v;
+}
+
+// Pass 1: one wave per column, 64 rows per step, wave-wide max-scans downwards (nearest
+// unflagged row above, strictly) and upwards (below), carried across chunks.
+__global__ __launch_bounds__(64) void lrc_cols_kernel(const uint8_t *__restrict__ f, int H, int W,
+                                                      uint32_t *__restrict__ park)
+{
+    const int x = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int nchunk = (H + 63) / 64;
+    int carry = -1;
+    for (int c = 0; c < nchunk; c++) {             // top -> bottom
+        const int y = c * 64 + lane;
+        const bool in = y < H;
+        const bool flagged = in && f[(size_t)y * W + x] == 1;
+        const int v = wave_max_scan(in && !flagged ? y : -1);
+        int prev = __shfl_up(v, 1, 64);
+        if (lane == 0) prev = -1;
+        const int up = prev > carry ? prev : carry;
+        const int last = __builtin_amdgcn_readlane(v, 63);
+        carry = last > carry ? last : carry;
+        if (flagged) park[(size_t)y * W + x] = up < 0 ? LRC_NONE : (uint32_t)up;
+    }
+    carry = -1;                                    // as H-1-y of the nearest unflagged row below
+    for (int c = 0; c < nchunk; c++) {             // bottom -> top
+        const int y = H - 1 - (c * 64 + lane);
+        const bool in = y >= 0;
+        const bool flagged = in && f[(size_t)(in ? y : 0) * W + x] == 1;
+        const int v = wave_max_scan(in && !flagged ? H - 1 - y : -1);
+        int prev = __shfl_up(v, 1, 64);
+        if (lane == 0) prev = -1;
+        const int dn = prev > carry ? prev : carry;
+        const int last = __builtin_amdgcn_readlane(v, 63);
+        carry = last > carry ? last : carry;
+        if (flagged) park[(size_t)y * W + x] |= (dn < 0 ? LRC_NONE : (uint32_t)(H - 1 - dn)) << 16;
+    }
+}
+
+__global__ __launch_bounds__(64) void lrc_rows_kernel(const float *__restrict__ dl, const uint8_t *__restrict__ f,
+                                                      int H, int W, float *__restrict__ out)
+{
+    // nearest unflagged column left of x (LRC_NONE = none): 2 B per column of the row, W <= 65535
+    extern __shared__ uint16_t sleft[];
+    const int y = blockIdx.x;
+    const int lane = threadIdx.x;
+    const size_t row = (size_t)y * W;
+    const uint32_t *park = reinterpret_cast<const uint32_t *>(out);
+    const int nchunk = (W + 63) / 64;
+    int carry = -1;
+    for (int c = 0; c < nchunk; c++) {             // left -> right
+        const int x = c * 64 + lane;
+        const bool in = x < W;
+        const bool clear = in && f[row + x] != 1;
+        const int v = wave_max_scan(clear ? x : -1);
+        int prev = __shfl_up(v, 1, 64);
+        if (lane == 0) prev = -1;
+        const int lft = prev > carry ? prev : carry;
+        if (in) sleft[x] = lft < 0 ? (uint16_t)LRC_NONE : (uint16_t)lft;
+        const int last = __builtin_amdgcn_readlane(v, 63);
+        carry = last > carry ? last : carry;
+    }
+    __syncthreads();
+    carry = -1;                                    // as W-1-x of the nearest unflagged column to the right
+    for (int c = 0; c < nchunk; c++) {             // right -> left
+        const int x = W - 1 - (c * 64 + lane);
+        const bool in = x >= 0;
+        const bool flagged = in && f[row + x] == 1;
+        const int v = wave_max_scan(in && !flagged ? W - 1 - x : -1);
+        int prev = __shfl_up(v, 1, 64);
+        if (lane == 0) prev = -1;
+        const int rr = prev > carry ? prev : carry;
+        const int last = __builtin_amdgcn_readlane(v, 63);
+        carry = last > carry ? last : carry;
+        if (!in) continue;
+        if (!flagged) {
+            out[row + x] = dl[row + x];
+            continue;
+        }
+        const uint32_t pk = park[row + x];
+        const uint32_t up = pk & 0xFFFFu, down = pk >> 16;
+        const int left = sleft[x] == LRC_NONE ? -1 : (int)sleft[x];
+        int number = 0;
+        double sum = 0.0;
+        if (up != LRC_NONE) { number++; sum += dl[(size_t)up * W + x]; }
+        if (down != LRC_NONE) { number++; sum += dl[(size_t)down * W + x]; }
+        if (rr >= 0) { number++; sum += dl[row + (W - 1 - rr)]; }
+        if (left >= 0) { number++; sum += dl[row + left]; }
+        out[row + x] = number > 0 ? (float)(sum / number) : dl[row + x];
+    }
+}
+
+__global__ __launch_bounds__(256) void median5_kernel(const float *__restrict__ src, int H, int W,
+                                                      float *__restrict__ dst)
+{
+    const int x = blockIdx.x * 16 + (threadIdx.x & 15) + 2;
+    const int y = blockIdx.y * 16 + (threadIdx.x >> 4) + 2;
+    if (y + 2 >= H || x + 2 >= W) return;
+    float w[25];
+#pragma unroll
+    for (int i = -2; i <= 2; i++)
+#pragma unroll
+        for (int j = -2; j <= 2; j++) w[(i + 2) * 5 + j + 2] = src[(size_t)(y + i) * W + x + j];
+    float cur = 0.0f;
+    // partial selection sort to the 13th smallest, same swaps as the reference
+    for (int i = 0; i < 13; i++) {
+        cur = w[i];
+        int ci = i;
+        for (int j = i + 1; j < 25; j++)
+            if (cur > w[j]) { cur = w[j]; ci = j; }
+        w[ci] = w[i];
+    }
+    dst[(size_t)y * W + x] = cur;
+}
+
+}  // namespace sde
+
+using namespace sde;
+
+SDE_EXPORT int sde_lr_check(const float *disp_l, const float *disp_r, int H, int W, uint8_t *lrc_l, uint8_t *lrc_r,
+                            void *stream)
+{
+    if (!disp_l || !disp_r || !lrc_l || !lrc_r || H <= 0 || W <= 0) return SDE_ERR_ARG;
+    lr_check_kernel<<<cdiv((int64_t)H * W, 256), 256, 0, as_stream(stream)>>>(disp_l, disp_r, H, W, lrc_l, lrc_r);
+    return launch_status();
+}
+
+SDE_EXPORT int sde_lrc_fill(const float *disp_l, const uint8_t *lrc_l, int H, int W, float *out, void *stream)
+{
+    if (!disp_l || !lrc_l || !out || H <= 0 || W <= 0) return SDE_ERR_ARG;
+    // 16-bit row / column indices (0xFFFF = none); the row pass keeps 2 B per column in LDS (<= 128 KB)
+    if (H >= (int)LRC_NONE || W >= (int)LRC_NONE || out == disp_l) return SDE_ERR_ARG;
+    hipStream_t st = as_stream(stream);
+    const size_t smem = 2 * (size_t)W;
+    if (smem > 64 * 1024) {
+        static std::atomic<uint64_t> attr{0};
+        once_per_device(attr, [] {
+            (void)hipFuncSetAttribute((const void *)lrc_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      2 * (int)LRC_NONE);
+        });
+    }
+    lrc_cols_kernel<<<W, 64, 0, st>>>(lrc_l, H, W, reinterpret_cast<uint32_t *>(out));
+    lrc_rows_kernel<<<H, 64, smem, st>>>(disp_l, lrc_l, H, W, out);
+    return launch_status();
+}
+
+SDE_EXPORT int sde_median5(const float *src, int H, int W, float *dst, void *stream)
+{
+    if (!src || !dst || H <= 0 || W <= 0) return SDE_ERR_ARG;
+    if (H < 5 || W < 5) return SDE_OK;   // no interior pixel
+    dim3 grid(cdiv(W - 4, 16), cdiv(H - 4, 16));
+    median5_kernel<<<grid, 256, 0, as_stream(stream)>>>(src, H, W, dst);
+    return launch_status();
+}

@@ -106,6 +106,38 @@ def test_sgm_single_nan_switches_one_line(gpu, oracle):
         assert same_s(got, want), d
 
 
+# (H, W, D), the NaN voxel, the +inf voxel (both off the image corner)
+TWO_PIXEL_LINES = [((2, 9, 64), (0, 4, 33), (1, 7, 2)),
+                   ((9, 2, 100), (4, 0, 33), (7, 1, 2)),
+                   ((3, 3, 192), (1, 1, 100), (0, 2, 5))]
+
+
+@pytest.mark.parametrize("shape,nan_at,inf_at", TWO_PIXEL_LINES)
+def test_sgm_faithful_on_two_pixel_lines(gpu, oracle, shape, nan_at, inf_at):
+    """The faithful path on the shortest lines: images 2 (or 3) pixels across, where a line of
+    length 2 visits n = 2 pixels -- all of it -- instead of the usual length - 1.  One NaN and one
+    +inf voxel, so nearly all of S stays finite and a wrong pixel sequence cannot hide behind NaN."""
+    from scenedepthestimation_amd import ops
+    H, W, D = shape
+    rng = np.random.default_rng(H * W + D)
+    cv = (rng.standard_normal((H, W, D)) * 0.5).astype(np.float32)
+    cv[nan_at] = np.nan
+    cv[inf_at] = np.inf
+    img = rng.integers(0, 256, (H, W)).astype(np.uint8)
+    pen = oracle.sgm_penalties(img)
+    want = oracle.sgm_8path(cv, pen)
+    assert np.isnan(want).any() and np.isfinite(want).mean() >= 0.9
+    for d in range(8):
+        got = host(ops.sgm_direction(dev(cv), dev(pen), d, torch.zeros((H, W, D), device="cuda")))
+        assert same_s(got, oracle.sgm_direction(cv, pen, d)), d
+    S = torch.empty((H, W, D), dtype=torch.float32, device="cuda").fill_(np.nan)
+    got = host(ops.sgm_8path_pair(dev(cv), dev(pen), S, accumulate=False, zero_du_penalties=True)[0])
+    assert same_s(got, want)
+    S = torch.empty((H, W, D), dtype=torch.float32, device="cuda")
+    disp = ops.sgm_8path_wta_pair(dev(cv), dev(pen), S, zero_du_penalties=True)[0]
+    assert np.array_equal(host(disp), oracle.wta_sgm(want))
+
+
 def test_disparity_compute_by_gpu_nonfinite_features(gpu, oracle):
     """The drop-in API with caller features holding NaN / inf (no finiteness precondition)."""
     from scenedepthestimation_amd import process_functional as pf

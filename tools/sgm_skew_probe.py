@@ -1,5 +1,6 @@
 """Placement sensitivity of the 7-launch SGM pair (1024^2 x 192) for the library and each tools/_var/libsde_sgm*.so
-variant build (tools/build_file_variant.sh sgm.hip sgm_NAME ...): for every library,
+variant build (tools/build_file_variant.sh sgm.hip sgm_NAME ...: sgm.hip is the file to rebuild, it includes
+the kernel's headers sgm_scan.h, sgm_faithful.h and sgm_wave.h): for every library,
 NSETS sets of the four volumes allocated one after another (the previous set held while the next is allocated --
 the allocation pattern that lands sets on different physical memory), each timed (median of 3).
 Prints every set's time and the median / min / max per library; disparities checked identical to the library's.

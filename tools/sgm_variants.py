@@ -1,6 +1,7 @@
 """Time sde_sgm_8path_wta_pair (both sides, 7 launches) of each tools/_var/libsde_sgm_<name>.so at
 H x W x D, interleaved over rounds; check every variant's S and disparity maps bit-identical to the
-first's."""
+first's.  A variant is a rebuild of csrc/sgm.hip, which includes the kernel (sgm_scan.h), the faithful path
+(sgm_faithful.h) and the wave primitives (sgm_wave.h): bash tools/build_file_variant.sh sgm.hip sgm_NAME [flags]."""
 import ctypes
 import glob
 import os
