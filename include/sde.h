@@ -104,6 +104,22 @@ int sde_cv_wta(const float *fl, const float *fr, int H, int W, int C, int d0, in
                void *stream);
 
 /*
+ * The right view of sde_cv_wta (additive in ABI 4): fused cost volume + WTA indexed by RIGHT pixel,
+ *   disp_r = flipW( WTA1( compute_cost_volume( flipW(fr), flipW(fl), D ) ) )      (d0 = 0, d1 = D)
+ * with the reference's own NumPy functions (process_functional.py:48-73 + :96-113) on the mirrored, swapped
+ * pair -- the standard right-matcher construction.  Equivalently, for right pixel x', the first minimum over d
+ * in [d0, d1) of cost(x'+d, d) = -(0.0f + pairwise_sum_c fl[y][x'+d][c]*fr[y][x'][c]); voxels with x'+d >= W
+ * hold the -0.0 fill and take part in the scan (as x < d does in the left view), the comparison is a strict
+ * `<` (ties -> lower d), and since the products commute every cost has the left view's bits.  fl / fr are the
+ * same left / right feature maps sde_cv_wta takes (not swapped by the caller).  Argument rules, modes (both
+ * bit-exact), the workspace (sde_cv_wta_workspace_bytes, same layout and counter words) and the outputs' meaning
+ * are sde_cv_wta's; shards over [d0, d1) merge with sde_argmin_merge as for the left view.
+ */
+int sde_cv_wta_right(const float *fl, const float *fr, int H, int W, int C, int d0, int d1, float *disp,
+                     float *min_cost, int32_t *argmin, int mode, void *workspace, int64_t workspace_bytes,
+                     void *stream);
+
+/*
  * Split a [npix][64] float32 feature map for SDE_CV_CERTIFIED: hi = bf16_rne(x),
  * lo = bf16_rne(x - hi) (both [npix][64] bf16 bit patterns) and norm[p] >= the
  * pixel's L2 norm.  The tower can emit the same three outputs from its last
@@ -399,6 +415,18 @@ int sde_cbca_reciprocals(double *out, int n, void *stream);
 /* is_error_match_kernel (process_functional.py:977-1000): lrc_l/lrc_r u8 [H][W], caller-zeroed. */
 int sde_lr_check(const float *disp_l, const float *disp_r, int H, int W, uint8_t *lrc_l, uint8_t *lrc_r,
                  void *stream);
+
+/*
+ * Left-right consistency without sde_lr_check's uint8 column cast (the reference indexes column (x -+ d) & 255,
+ * which checks consistency only for W <= 256).  The same float64 arithmetic with the column taken as the plain
+ * truncated integer; lrc_l / lrc_r u8 [H][W], every pixel written (no zeroing needed), max_diff >= 0:
+ *   lrc_l = 1 iff d = disp_l[y][x] < 0, or x - d >= 0 and |d - disp_r[y][(int)(x-d)]| > max_diff; else 0
+ *   lrc_r = 1 iff d = disp_r[y][x] < 0, or x + d <  W and |d - disp_l[y][(int)(x+d)]| > max_diff; else 0
+ * Never reads outside the row.  For W <= 256, non-negative disparities and max_diff = 1 it equals sde_lr_check
+ * on zeroed buffers.  Composes with sde_cv_wta / sde_cv_wta_right, sde_lrc_fill and sde_median5.
+ */
+int sde_lr_consistency(const float *disp_l, const float *disp_r, int H, int W, float max_diff, uint8_t *lrc_l,
+                       uint8_t *lrc_r, void *stream);
 
 /* LRC_kernel left output (process_functional.py:1003-1088).  Two linear scans instead of
  * the reference's per-pixel walks; `out` doubles as scratch, so out != disp_l.  Requires

@@ -44,6 +44,8 @@ SIGNATURES = {
     "sde_cv_wta_workspace_bytes": (c_int64, [c_int, c_int]),
     "sde_cv_wta": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                            c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "sde_cv_wta_right": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_int, c_void_p, c_int64, c_void_p]),
     "sde_feature_split": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sde_cv_wta_split_workspace_bytes": (c_int64, [c_int, c_int]),
     "sde_cv_wta_split": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -84,6 +86,7 @@ SIGNATURES = {
     "sde_cbca_lr": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p, ctypes.c_size_t, c_void_p]),
     "sde_cbca_reciprocals": (c_int, [c_void_p, c_int, c_void_p]),
     "sde_lr_check": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sde_lr_consistency": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "sde_lrc_fill": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sde_median5": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }

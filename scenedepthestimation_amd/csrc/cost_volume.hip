@@ -504,7 +504,12 @@ __global__ __launch_bounds__(256) void cv_generic_kernel(const float *__restrict
     int arg = -1;
     for (int d = d0; d < d1; d++) {
         float cost = invalid;
-        if (x >= d) cost = np_neg_dot(fl + ((size_t)y * W + x) * C, fr + ((size_t)y * W + x - d) * C, C);
+        if (OUT == OUT_WTA && sides == SDE_SIDE_RIGHT) {
+            // the right view's scan: cost(x + d, d) for right pixel x
+            if (x + d < W) cost = np_neg_dot(fl + ((size_t)y * W + x + d) * C, fr + ((size_t)y * W + x) * C, C);
+        } else if (x >= d) {
+            cost = np_neg_dot(fl + ((size_t)y * W + x) * C, fr + ((size_t)y * W + x - d) * C, C);
+        }
         if (OUT == OUT_WTA) {
             if (cost < best) { best = cost; arg = d; }
         } else if (OUT == OUT_DHW) {
@@ -832,9 +837,13 @@ __global__ __launch_bounds__(256) void cv_wta_cert_kernel(const float *__restric
 // give the sequential first minimum.  All of a wave's iterations are in flight at once up to D = 256 (a
 // chunk): one round of loads per pixel instead of a lane's three to four dependent 16-load dots, whose
 // 64 lanes each read another pixel's 256 B (64 cache lines per load instruction).
+// RIGHT: the right view's scan -- the listed pixel x owns own[p] = fr[p], the other operand is fl at x + d, valid
+// iff x + d < W (the load index is clamped, as x - d is in the left form); the same per-disparity arithmetic
+// (the products commute) and merge order.  own / other: (fl, fr) for the left view, (fr, fl) for the right.
 constexpr int FX2_U = 8;   // iterations per round of loads
-__global__ __launch_bounds__(256) void cv_wta_fixup_kernel(const float *__restrict__ fl, const float *__restrict__ fr,
-                                                           int W, int d0, int d1, const unsigned *__restrict__ counter,
+template <bool RIGHT>
+__global__ __launch_bounds__(256) void cv_wta_fixup_kernel(const float *__restrict__ own,
+                                                           const float *__restrict__ other, int W, int d0, int d1, const unsigned *__restrict__ counter,
                                                            const int32_t *__restrict__ list, float *__restrict__ out_min,
                                                            int32_t *__restrict__ out_arg, float *__restrict__ out_disp)
 {
@@ -851,15 +860,15 @@ __global__ __launch_bounds__(256) void cv_wta_fixup_kernel(const float *__restri
         const size_t rowbase = p - x;
         float av[8];
 #pragma unroll
-        for (int m = 0; m < 8; m++) av[m] = fl[p * 64 + 8 * m + jj];
+        for (int m = 0; m < 8; m++) av[m] = own[p * 64 + 8 * m + jj];
         float best = __builtin_inff();
         int arg = -1;
         for (int db = dw; db < dwe; db += 8 * FX2_U) {
             float bv[FX2_U][8];
 #pragma unroll
             for (int u = 0; u < FX2_U; u++) {
-                const int xr = x - (db + 8 * u + g);
-                const float *b = fr + (rowbase + (xr >= 0 ? xr : 0)) * 64 + jj;
+                const int xr = RIGHT ? x + (db + 8 * u + g) : x - (db + 8 * u + g);
+                const float *b = other + (rowbase + (RIGHT ? (xr < W ? xr : W - 1) : (xr >= 0 ? xr : 0))) * 64 + jj;
 #pragma unroll
                 for (int m = 0; m < 8; m++) bv[u][m] = b[8 * m];
             }
@@ -872,7 +881,7 @@ __global__ __launch_bounds__(256) void cv_wta_fixup_kernel(const float *__restri
                 acc = acc + __shfl_xor(acc, 1, 64);   // (acc0 + acc1), (acc2 + acc3), ...
                 acc = acc + __shfl_xor(acc, 2, 64);   // ((acc0 + acc1) + (acc2 + acc3)), ...
                 acc = acc + __shfl_xor(acc, 4, 64);
-                const float c = x - d >= 0 ? -(0.0f + acc) : -0.0f;
+                const float c = (RIGHT ? x + d < W : x - d >= 0) ? -(0.0f + acc) : -0.0f;
                 if (d < dwe && c < best) {
                     best = c;
                     arg = d;
@@ -1027,7 +1036,7 @@ SDE_EXPORT int sde_cv_wta_split(const float *fl, const float *fr, const uint16_t
         fl, fr, reinterpret_cast<const uint4 *>(fl_hi), reinterpret_cast<const uint4 *>(fl_lo), fl_norm,
         reinterpret_cast<const uint4 *>(fr_hi), reinterpret_cast<const uint4 *>(fr_lo), fr_norm, H, W, d0, d1,
         min_cost, argmin, disp, counter, list);
-    cv_wta_fixup_kernel<<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, counter, list, min_cost, argmin, disp);
+    cv_wta_fixup_kernel<false><<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, counter, list, min_cost, argmin, disp);
     return launch_status();
 }
 
@@ -1035,9 +1044,11 @@ SDE_EXPORT int sde_cv_wta_split(const float *fl, const float *fr, const uint16_t
 // most 13 tiles of 32 whatever its first disparity: every chunk fits the row sweep's ring (row_cert_supported)
 constexpr int ROW_CHUNK = 256;
 
-SDE_EXPORT int sde_cv_wta(const float *fl, const float *fr, int H, int W, int C, int d0, int d1, float *disp,
-                          float *min_cost, int32_t *argmin, int mode, void *workspace, int64_t workspace_bytes,
-                          void *stream)
+// sde_cv_wta (right = false) and sde_cv_wta_right: the same dispatch, workspace and chunk loop; the right view
+// runs the mirrored row sweep, the right-view fix-up and the exact kernels' SDE_SIDE_RIGHT forms
+static int cv_wta_view(bool right, const float *fl, const float *fr, int H, int W, int C, int d0, int d1, float *disp,
+                       float *min_cost, int32_t *argmin, int mode, void *workspace, int64_t workspace_bytes,
+                       void *stream)
 {
     if (!fl || !fr || H <= 0 || W <= 0 || C <= 0 || d0 < 0 || d1 <= d0) return SDE_ERR_ARG;
     if (!disp && !min_cost && !argmin) return SDE_ERR_ARG;
@@ -1045,8 +1056,17 @@ SDE_EXPORT int sde_cv_wta(const float *fl, const float *fr, int H, int W, int C,
     hipStream_t st = as_stream(stream);
     auto exact64 = [&] {
         dim3 grid(cdiv(W, CV_TX), H);
-        cv64_kernel<SDE_SIDE_LEFT, OUT_WTA><<<grid, 256, 0, st>>>(fl, fr, H, W, d0, d1, 0, -0.0f, nullptr, min_cost,
-                                                                   argmin, disp);
+        if (right)
+            cv64_kernel<SDE_SIDE_RIGHT, OUT_WTA><<<grid, 256, 0, st>>>(fr, fl, H, W, d0, d1, 0, -0.0f, nullptr,
+                                                                        min_cost, argmin, disp);
+        else
+            cv64_kernel<SDE_SIDE_LEFT, OUT_WTA><<<grid, 256, 0, st>>>(fl, fr, H, W, d0, d1, 0, -0.0f, nullptr,
+                                                                       min_cost, argmin, disp);
+    };
+    // exact resolution of the pixels a sweep over [a, b) listed
+    auto fixup = [&](int a, int b, unsigned *cnt, const int32_t *lst, float *mn, int32_t *ag, float *dp) {
+        if (right) cv_wta_fixup_kernel<true><<<1024, 256, 0, st>>>(fr, fl, W, a, b, cnt, lst, mn, ag, dp);
+        else cv_wta_fixup_kernel<false><<<1024, 256, 0, st>>>(fl, fr, W, a, b, cnt, lst, mn, ag, dp);
     };
     if (C == 64 && mode == SDE_CV_CERTIFIED) {
         // The row-sweep kernel straight from the fp32 features (cv_row.hip) + the exact fix-ups of the pixels it
@@ -1061,8 +1081,8 @@ SDE_EXPORT int sde_cv_wta(const float *fl, const float *fr, int H, int W, int C,
         int32_t *list = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(workspace) + 256);
         if (hipMemsetAsync(counter, 0, CERT_COUNTERS * sizeof(unsigned), st) != hipSuccess) return SDE_ERR_LAUNCH;
         if (row_cert_supported(d0, d1)) {
-            launch_row_cert(fl, fr, H, W, d0, d1, min_cost, argmin, disp, counter, list, st);
-            cv_wta_fixup_kernel<<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, counter, list, min_cost, argmin, disp);
+            launch_row_cert(fl, fr, H, W, d0, d1, min_cost, argmin, disp, counter, list, st, nullptr, right);
+            fixup(d0, d1, counter, list, min_cost, argmin, disp);
         } else if (K <= CERT_COUNTERS) {
             // each chunk's outputs are the exact kernel's on its range (as for the disparity shards of
             // parallel.py).  Chunk k counts its fix-ups in counter word k; the list is reused: chunk k's fix-ups
@@ -1073,8 +1093,9 @@ SDE_EXPORT int sde_cv_wta(const float *fl, const float *fr, int H, int W, int C,
                 const int a = d0 + k * ROW_CHUNK, b = std::min(d1, a + ROW_CHUNK);
                 float *mk = cmin + (size_t)k * npix;
                 int32_t *ak = carg + (size_t)k * npix;
-                launch_row_cert(fl, fr, H, W, a, b, mk, ak, nullptr, counter + k, list, st, k > 0 ? mk - npix : nullptr);
-                cv_wta_fixup_kernel<<<1024, 256, 0, st>>>(fl, fr, W, a, b, counter + k, list, mk, ak, nullptr);
+                launch_row_cert(fl, fr, H, W, a, b, mk, ak, nullptr, counter + k, list, st, k > 0 ? mk - npix : nullptr,
+                                right);
+                fixup(a, b, counter + k, list, mk, ak, nullptr);
             }
             argmin_chunks_kernel<<<cdiv(npix, 256), 256, 0, st>>>(cmin, carg, K, npix, disp, min_cost, argmin);
         } else {
@@ -1084,10 +1105,27 @@ SDE_EXPORT int sde_cv_wta(const float *fl, const float *fr, int H, int W, int C,
         exact64();
     } else {
         const int blocks = cdiv((int64_t)H * W, 256);
-        cv_generic_kernel<OUT_WTA><<<blocks, 256, 0, st>>>(fl, fr, H, W, C, d0, d1, 0, SDE_SIDE_LEFT, -0.0f,
-                                                            nullptr, nullptr, min_cost, argmin, disp);
+        cv_generic_kernel<OUT_WTA><<<blocks, 256, 0, st>>>(fl, fr, H, W, C, d0, d1, 0,
+                                                            right ? SDE_SIDE_RIGHT : SDE_SIDE_LEFT, -0.0f, nullptr,
+                                                            nullptr, min_cost, argmin, disp);
     }
     return launch_status();
+}
+
+SDE_EXPORT int sde_cv_wta(const float *fl, const float *fr, int H, int W, int C, int d0, int d1, float *disp,
+                          float *min_cost, int32_t *argmin, int mode, void *workspace, int64_t workspace_bytes,
+                          void *stream)
+{
+    return cv_wta_view(false, fl, fr, H, W, C, d0, d1, disp, min_cost, argmin, mode, workspace, workspace_bytes,
+                       stream);
+}
+
+SDE_EXPORT int sde_cv_wta_right(const float *fl, const float *fr, int H, int W, int C, int d0, int d1, float *disp,
+                                float *min_cost, int32_t *argmin, int mode, void *workspace, int64_t workspace_bytes,
+                                void *stream)
+{
+    return cv_wta_view(true, fl, fr, H, W, C, d0, d1, disp, min_cost, argmin, mode, workspace, workspace_bytes,
+                       stream);
 }
 
 SDE_EXPORT int sde_wta(const float *vol, int H, int W, int D, int layout, int rule, float *disp, void *stream)

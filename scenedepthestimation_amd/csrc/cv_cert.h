@@ -81,9 +81,10 @@ __device__ __forceinline__ int xcd_remap(int b, int nb)
 
 constexpr float FX_NORM_UP = 1.000004f;
 
-// the row-sweep kernel (cv_row.hip): window size limit and launcher
+// the row-sweep kernel (cv_row.hip): window size limit and launcher (mirror: the right view)
 bool row_cert_supported(int d0, int d1);
 void launch_row_cert(const float *fl, const float *fr, int H, int W, int d0, int d1, float *out_min, int32_t *out_arg,
-                     float *out_disp, unsigned *counter, int32_t *list, hipStream_t st, const float *prev_min = nullptr);
+                     float *out_disp, unsigned *counter, int32_t *list, hipStream_t st, const float *prev_min = nullptr,
+                     bool mirror = false);
 
 }  // namespace sde

@@ -38,6 +38,17 @@ namespace sde {
 // best fast score beats the runner-up by more than 2 eps, the fast argmax is the exact first
 // minimum, and its exact cost is recomputed from the fp32 rows (L2-resident) when requested; every
 // other pixel goes to the fix-up list.  Outputs are bit-identical to the exact kernel.
+//
+// Right view (MIRROR): disp_r = flipW(WTA1(compute_cost_volume(flipW(fr), flipW(fl), D))), i.e. for right pixel
+// x' the first minimum over d of cost(x' + d, d) = -(0 + fl[x' + d] . fr[x']), voxels with x' + d >= W the -0.0
+// fill.  The kernel runs the sweep above unchanged in mirrored coordinates xm = W - 1 - x: the owning pixels come
+// from fr, the staged ring from fl, and "x" in the text above (tiles, band bounds Ta / Tb, score modes, `none`,
+// the certificate) is xm.  Only the places that turn a row coordinate into an address map it back (rw_col: the
+// ring and owner loads, the winner's exact cost, the pixel index of the outputs, prev_min and the fix-up list,
+// whose entries stay true pixel indices), so the partial tile and the partial superstrip of a row sit at the
+// low-x end of the true row.  The products commute, so every score and exact cost has the left view's bits on
+// the mirrored pair; the bound below is symmetric in its two operands (RW_K |a| |b| + RW_ABS (|a| + |b|)), so no
+// constant changes.
 // ---------------------------------------------------------------------------
 // Arithmetic of the fast scores and their bound (the chunked kernels of cost_volume.hip use bf16
 // hi/lo instead): every operand is scaled by 2^RW_S (exact) and split into two fp16 parts, x*2^S =
@@ -83,12 +94,21 @@ __device__ __forceinline__ void rw_split2(float x0, float x1, uint32_t &hi, uint
 
 constexpr int RW_T = 32;          // pixels per tile (= one MFMA N-tile of left pixels)
 
-// one 16-B unit (pixel u>>4, channels 4(u&15)..+3) of right tile T (zero outside the row)
+// the column of the true row that holds sweep coordinate x (0 <= x < W): x itself, W - 1 - x in the mirrored form
+template <bool MIRROR>
+__device__ __forceinline__ int rw_col(int x, int W)
+{
+    if constexpr (MIRROR) return W - 1 - x;
+    else return x;
+}
+
+// one 16-B unit (pixel u>>4, channels 4(u&15)..+3) of ring tile T (zero outside the row)
+template <bool MIRROR>
 __device__ __forceinline__ float4 rw_load(const float *__restrict__ frrow, int W, int T, int u)
 {
     const int xr = T * RW_T + (u >> 4);
     const bool ok = xr >= 0 && xr < W;
-    const float4 v = reinterpret_cast<const float4 *>(frrow)[(size_t)(ok ? xr : 0) * 16 + (u & 15)];
+    const float4 v = reinterpret_cast<const float4 *>(frrow)[(size_t)rw_col<MIRROR>(ok ? xr : 0, W) * 16 + (u & 15)];
     return ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
@@ -107,10 +127,11 @@ constexpr int R2_LEAD = 2;                 // scores issued before the next tile
 // the plain form in round 5, DESIGN "Round 5 status")
 
 // one stager lane's 8 units (pixel u >> 4, channels 4 (u & 15) ..) of right tile T: unit u = lane + 64 i
+template <bool MIRROR>
 __device__ __forceinline__ void r2_load(const float *__restrict__ frrow, int W, int T, int lane, float4 (&v)[8])
 {
 #pragma unroll
-    for (int i = 0; i < 8; i++) v[i] = rw_load(frrow, W, T, lane + 64 * i);
+    for (int i = 0; i < 8; i++) v[i] = rw_load<MIRROR>(frrow, W, T, lane + 64 * i);
 }
 
 // split a loaded tile into ring slot `slot`; its max squared pixel norm and non-finite flag
@@ -157,7 +178,8 @@ __device__ __forceinline__ void r2_store(uint4 *ring, unsigned *tmax, unsigned *
 // whose every exact score here is provably below -prev_min (best fast score + eps, with a factor 2 for the add's
 // rounding) has every cost above the previous chunk's minimum, so this chunk cannot win the in-order merge: it
 // writes (+inf, -1) and skips the certificate and the fix-up.
-template <bool WANT_MIN>
+// MIRROR: the right view (see the mapping above); fl / fr are the caller's maps in both forms.
+template <bool WANT_MIN, bool MIRROR>
 __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restrict__ fl, const float *__restrict__ fr,
                                                           int H, int W, int d0, int d1, int tlo0, int nw, int nt,
                                                           float *__restrict__ out_min, int32_t *__restrict__ out_arg,
@@ -172,8 +194,8 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 31, h = lane >> 5;
-    const float *flrow = fl + (size_t)y * W * 64;
-    const float *frrow = fr + (size_t)y * W * 64;
+    const float *flrow = (MIRROR ? fr : fl) + (size_t)y * W * 64;   // the owning pixels' row
+    const float *frrow = (MIRROR ? fl : fr) + (size_t)y * W * 64;   // the ring's row
     const size_t rowpix = (size_t)y * W;
     const int nss = (W + R2_NX - 1) / R2_NX;
     auto slot_of = [&](int T) { int r = T % nt; return r < 0 ? r + nt : r; };
@@ -192,8 +214,8 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
             float4 pv[PB][8];
 #pragma unroll
             for (int i = 0; i < PB; i++)
-                if (sw + 4 * (PB * b + i) < nw) r2_load(frrow, W, tlo0 + sw + 4 * (PB * b + i), lane, pv[i]);
-            if (b == 4 / PB - 1 && nss > 1) r2_load(frrow, W, tlo0 + nw + sw, lane, nv);
+                if (sw + 4 * (PB * b + i) < nw) r2_load<MIRROR>(frrow, W, tlo0 + sw + 4 * (PB * b + i), lane, pv[i]);
+            if (b == 4 / PB - 1 && nss > 1) r2_load<MIRROR>(frrow, W, tlo0 + nw + sw, lane, nv);
 #pragma unroll
             for (int i = 0; i < PB; i++)
                 if (sw + 4 * (PB * b + i) < nw) r2_store(ring, tmax, tbad, slot_of(tlo0 + sw + 4 * (PB * b + i)), lane, pv[i]);
@@ -205,7 +227,7 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
             if (k + 1 < nss) {
                 const int T = tlo0 + R2_NEW * (k + 1) + nw - R2_NEW + sw;
                 r2_store(ring, tmax, tbad, slot_of(T), lane, nv);
-                if (k + 2 < nss) r2_load(frrow, W, T + R2_NEW, lane, nv);
+                if (k + 2 < nss) r2_load<MIRROR>(frrow, W, T + R2_NEW, lane, nv);
             }
             __syncthreads();
         }
@@ -217,7 +239,8 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
     float4 lraw[8];
     auto load_left = [&](int kk) {
         const int xx = kk * R2_NX + RW_T * grp + j;
-        const float4 *src = reinterpret_cast<const float4 *>(flrow) + (size_t)(xx < W ? xx : 0) * 16 + 2 * h;
+        const float4 *src =
+            reinterpret_cast<const float4 *>(flrow) + (size_t)rw_col<MIRROR>(xx < W ? xx : 0, W) * 16 + 2 * h;
 #pragma unroll
         for (int s2 = 0; s2 < 4; s2++) { lraw[2 * s2] = src[4 * s2]; lraw[2 * s2 + 1] = src[4 * s2 + 1]; }
     };
@@ -410,8 +433,16 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                 const int ab = h ? (int)lo_arg : arg;   // the upper half takes lane j's merged arg
                 const int xr = x - ab;
                 const bool ok = xok && ab >= 0 && xr >= 0;
-                const float4 *la = reinterpret_cast<const float4 *>(flrow + (size_t)(xok ? x : 0) * 64) + h;
-                const float4 *ra = reinterpret_cast<const float4 *>(frrow + (size_t)(ok ? xr : 0) * 64) + h;
+                // (the two forms written out rather than through rw_col: the left form then compiles to the
+                // instructions it had before the mirrored one existed)
+                const float4 *la, *ra;
+                if constexpr (MIRROR) {
+                    la = reinterpret_cast<const float4 *>(flrow + (size_t)(W - 1 - (xok ? x : 0)) * 64) + h;
+                    ra = reinterpret_cast<const float4 *>(frrow + (size_t)(W - 1 - (ok ? xr : 0)) * 64) + h;
+                } else {
+                    la = reinterpret_cast<const float4 *>(flrow + (size_t)(xok ? x : 0) * 64) + h;
+                    ra = reinterpret_cast<const float4 *>(frrow + (size_t)(ok ? xr : 0) * 64) + h;
+                }
                 float4 lv[8], rv[8];
 #pragma unroll
                 for (int m = 0; m < 8; m++) {
@@ -438,7 +469,7 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
             // scores are scaled by 2^2S (exact): compare against the scaled bound
             const float nr = sqrtf(__uint_as_float(nmax2)) * FX_NORM_UP;
             const float eps = (RW_K * nl * nr + RW_ABS * (nl + nr) + FX_ABS) * (RW_SCALE * RW_SCALE);
-            const size_t p = rowpix + x;
+            const size_t p = rowpix + rw_col<MIRROR>(x, W);   // the true pixel (outputs, prev_min, list)
             // x < d0: no voxel of the band is inside the image -- every cost is the -0.0 fill, so the scan's
             // first minimum is d0 whatever the features hold
             const bool none = x < d0;
@@ -486,23 +517,35 @@ static RowWindow row_window(int d0, int d1)
 // the stagers' prologue holds at most 4 tiles each (nw <= 14 + the window-1 tile); ring <= 18 tiles, 144 KB
 bool row_cert_supported(int d0, int d1) { return row_window(d0, d1).nw <= 14; }
 
+// mirror: the right view (outputs indexed by right pixel)
 void launch_row_cert(const float *fl, const float *fr, int H, int W, int d0, int d1, float *out_min, int32_t *out_arg,
-                     float *out_disp, unsigned *counter, int32_t *list, hipStream_t st, const float *prev_min)
+                     float *out_disp, unsigned *counter, int32_t *list, hipStream_t st, const float *prev_min,
+                     bool mirror)
 {
     static std::atomic<uint64_t> attr{0};
     once_per_device(attr, [] {
-        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<true>,
+        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<true, false>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<false>,
+        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<false, false>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<true, true>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<false, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     });
     const RowWindow w = row_window(d0, d1);
-    if (out_min)
-        cv_wta_row2_kernel<true><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, out_min, out_arg,
-                                                          out_disp, counter, list, prev_min);
+    if (out_min && mirror)
+        cv_wta_row2_kernel<true, true><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, out_min,
+                                                                out_arg, out_disp, counter, list, prev_min);
+    else if (out_min)
+        cv_wta_row2_kernel<true, false><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, out_min,
+                                                                 out_arg, out_disp, counter, list, prev_min);
+    else if (mirror)
+        cv_wta_row2_kernel<false, true><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, nullptr,
+                                                                 out_arg, out_disp, counter, list, nullptr);
     else
-        cv_wta_row2_kernel<false><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, nullptr, out_arg,
-                                                           out_disp, counter, list, nullptr);
+        cv_wta_row2_kernel<false, false><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, nullptr,
+                                                                  out_arg, out_disp, counter, list, nullptr);
 }
 
 }  // namespace sde

@@ -30,6 +30,43 @@ __global__ __launch_bounds__(256) void lr_check_kernel(const float *__restrict__
     }
 }
 
+// Left-right consistency without lr_check_kernel's uint8 column cast (which compares against column (x -+ d) & 255:
+// the reference's arithmetic, a consistency check only for W <= 256).  The same float64 arithmetic with the column
+// taken as the plain truncated integer: a pixel is flagged (1) when its disparity d is negative (no winner), or
+// when its counterpart -- x - d in the right map for a left pixel, x + d in the left map for a right pixel -- is
+// inside the row and the two disparities differ by more than max_diff; every other pixel gets 0.  Every pixel is
+// written (no caller zeroing).  The column is in [0, x] (0 <= d <= x) or [x, W - 1] (d >= 0, x + d < W): never
+// outside the row; a NaN disparity fails every compare and gets 0, as in lr_check_kernel.
+__global__ __launch_bounds__(256) void lr_consistency_kernel(const float *__restrict__ dl, const float *__restrict__ dr,
+                                                             int H, int W, double max_diff,
+                                                             uint8_t *__restrict__ lrcl, uint8_t *__restrict__ lrcr)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (int64_t)H * W) return;
+    const int y = (int)(p / W), x = (int)(p % W);
+    const size_t row = (size_t)y * W;
+    const double ld = dl[p];
+    const double xr = (double)x - ld;
+    uint8_t fl = 0;
+    if (ld < 0) {
+        fl = 1;
+    } else if (xr >= 0) {
+        const double mn = ld - (double)dr[row + (int)xr];
+        fl = (mn > max_diff || mn < -max_diff) ? 1 : 0;
+    }
+    lrcl[p] = fl;
+    const double rd = dr[p];
+    const double xl = (double)x + rd;
+    uint8_t fr = 0;
+    if (rd < 0) {
+        fr = 1;
+    } else if (xl < W) {
+        const double mn = rd - (double)dl[row + (int)xl];
+        fr = (mn > max_diff || mn < -max_diff) ? 1 : 0;
+    }
+    lrcr[p] = fr;
+}
+
 // LRC_kernel (:1003-1088): every flagged pixel takes the mean of the nearest unflagged
 // pixel above, below, to the right and to the left (each only if it exists), summed in
 // that order in float64.  The reference walks each direction pixel by pixel, which is
@@ -174,6 +211,15 @@ SDE_EXPORT int sde_lr_check(const float *disp_l, const float *disp_r, int H, int
 {
     if (!disp_l || !disp_r || !lrc_l || !lrc_r || H <= 0 || W <= 0) return SDE_ERR_ARG;
     lr_check_kernel<<<cdiv((int64_t)H * W, 256), 256, 0, as_stream(stream)>>>(disp_l, disp_r, H, W, lrc_l, lrc_r);
+    return launch_status();
+}
+
+SDE_EXPORT int sde_lr_consistency(const float *disp_l, const float *disp_r, int H, int W, float max_diff,
+                                  uint8_t *lrc_l, uint8_t *lrc_r, void *stream)
+{
+    if (!disp_l || !disp_r || !lrc_l || !lrc_r || H <= 0 || W <= 0 || !(max_diff >= 0.0f)) return SDE_ERR_ARG;
+    lr_consistency_kernel<<<cdiv((int64_t)H * W, 256), 256, 0, as_stream(stream)>>>(disp_l, disp_r, H, W,
+                                                                                    (double)max_diff, lrc_l, lrc_r);
     return launch_status();
 }
 

@@ -1,7 +1,7 @@
 """Drop-in for the reference's match_single.py / match_single_ui.py entry points.
 
     python -m scenedepthestimation_amd.match_single [-g GPU] [-i ID] [-f FILE]
-           [--checkpoint PATH|synthetic] [--cpu-path] [--ndisp N] [--ui]
+           [--checkpoint PATH|synthetic] [--cpu-path [--lr-check]] [--ndisp N] [--ui]
 
 Same flags, paths and outputs as match_single.py:15-57 (and, with --ui,
 match_single_ui.py:20-58): reads ``./eval/left_{id}.png`` / ``right_{id}.png``
@@ -12,7 +12,10 @@ GPU path (disparity_compute_by_gpu) and writes ``./result/{file}/ld{id}.png`` as
 
 --cpu-path selects the reference's commented CPU alternative
 ``WTA1(compute_cost_volume(fl, fr, 128))`` (match_single.py:51-53), computed by
-the fused GPU kernel, bit-identical to the NumPy path.
+the fused GPU kernel, bit-identical to the NumPy path.  --lr-check (with --cpu-path
+only) writes that path's left map after the reference's post-processing instead
+(StereoMatcher.match_lr: the right view's map, the left-right check, LRC fill and
+the 5x5 median of process_functional.py:977-1088, :840-879).
 """
 from __future__ import annotations
 
@@ -35,6 +38,8 @@ def build_parser(ui: bool = False):
     p.add_argument("--checkpoint", type=str, default=DEFAULT_CKPT,
                    help="weights: .npz/.safetensors with conv{k}/weights:0, conv{k}/biases:0, or 'synthetic[:seed]'")
     p.add_argument("--cpu-path", action="store_true", help="WTA1(compute_cost_volume(...)) instead of the SGM path")
+    p.add_argument("--lr-check", action="store_true",
+                   help="with --cpu-path: left-right check, LRC fill and 5x5 median on the fused kernels' two views")
     p.add_argument("--ndisp", type=int, default=128, help="disparity range (the reference hard-codes 128)")
     p.add_argument("--ui", action="store_true", default=ui, help="match_single_ui.py paths and x2 output scaling")
     return p
@@ -44,6 +49,33 @@ def normalise(img_f32):
     """match_single.py:40-43: per-image (I - mean) / std over axes (0,1), then a channel axis."""
     x = (img_f32 - np.mean(img_f32, axis=(0, 1))) / np.std(img_f32, axis=(0, 1))
     return np.expand_dims(x, axis=2)
+
+
+def parse_args(argv=None, ui: bool = False):
+    p = build_parser(ui)
+    args = p.parse_args(argv)
+    if args.lr_check and not args.cpu_path:
+        p.error("--lr-check needs --cpu-path (the SGM path has its own left-right check)")
+    return args
+
+
+def lr_checked_disparity(left, right, ndisp, checkpoint):
+    """The --lr-check map: compute_feature's tower on the normalised images (the same padded input, so the same
+    features as the plain --cpu-path run), then StereoMatcher.lr_checked on them."""
+    import torch
+
+    from . import mc_cnn
+    from .pipeline import StereoMatcher
+    nlayers = 11 // 2
+    H, W = left.shape[:2]
+    m = StereoMatcher(H, W, ndisp, weights=mc_cnn.load_weights(checkpoint, nlayers), nlayers=nlayers)
+    for i, img in enumerate((left, right)):
+        buf = np.zeros((H + 2 * nlayers, W + 2 * nlayers), np.float32)
+        buf[nlayers:nlayers + H, nlayers:nlayers + W] = img[..., 0]
+        m.img_pad[i].copy_(torch.from_numpy(buf))
+    m.features_from_padded()
+    disp, _, _ = m.lr_checked()
+    return disp.cpu().numpy()
 
 
 def run(args) -> str:
@@ -63,12 +95,15 @@ def run(args) -> str:
         raise AttributeError(f"'NoneType' object has no attribute 'astype' (cannot read {lp} / {rp})")
     left = normalise(_left.astype(np.float32))
     right = normalise(_right.astype(np.float32))
-    fl, fr = compute_feature(left, right, 11, 11, 64, args.checkpoint)
-    if args.cpu_path:
-        disp = WTA1(compute_cost_volume(fl, fr, args.ndisp))
+    if args.cpu_path and getattr(args, "lr_check", False):
+        disp = lr_checked_disparity(left, right, args.ndisp, args.checkpoint)
     else:
-        detail_time = np.zeros(shape=[7], dtype=np.float32)
-        disp, _, detail_time = disparity_compute_by_gpu(_left, _right, fl, fr, detail_time, ndisp=args.ndisp)
+        fl, fr = compute_feature(left, right, 11, 11, 64, args.checkpoint)
+        if args.cpu_path:
+            disp = WTA1(compute_cost_volume(fl, fr, args.ndisp))
+        else:
+            detail_time = np.zeros(shape=[7], dtype=np.float32)
+            disp, _, detail_time = disparity_compute_by_gpu(_left, _right, fl, fr, detail_time, ndisp=args.ndisp)
     out = disp.astype("uint8") * 2 if args.ui else disp.astype("uint8")
     path = "./result/{}/ld{}.png".format(args.file, args.id)
     imageio.imwrite(path, out)
@@ -76,7 +111,7 @@ def run(args) -> str:
 
 
 def main(argv=None, ui: bool = False):
-    args = build_parser(ui).parse_args(argv)
+    args = parse_args(argv, ui)
     path = run(args)
     print(path, file=sys.stderr)
 

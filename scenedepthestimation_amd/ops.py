@@ -101,6 +101,21 @@ def cv_wta(fl, fr, d0: int, d1: int, disp=None, min_cost=None, argmin=None, want
     sweep + error bound, exact resolution of uncertified pixels): identical outputs.  workspace: uint8
     tensor of cv_wta_workspace_bytes(H, W) bytes (allocated if None); cv_wta_fixups(workspace) is the
     number of pixels resolved exactly after the call."""
+    return _cv_wta_view(lib.sde_cv_wta, "sde_cv_wta", fl, fr, d0, d1, disp, min_cost, argmin, want, mode, workspace)
+
+
+def cv_wta_right(fl, fr, d0: int, d1: int, disp=None, min_cost=None, argmin=None, want=("disp",),
+                 mode: str = "certified", workspace=None):
+    """The right view of cv_wta (sde_cv_wta_right), indexed by right pixel: the first minimum over [d0, d1) of
+    cost(x + d, d), i.e. flipW(WTA1(compute_cost_volume(flipW(fr), flipW(fl), d1))) when d0 = 0 (voxels with
+    x + d >= W hold the -0.0 fill; ties go to the lower d).  fl / fr are the left / right maps as for cv_wta.
+    Same arguments, modes (identical outputs), workspace and returns as cv_wta; cv_wta_fixups(workspace) counts
+    the pixels resolved exactly."""
+    return _cv_wta_view(lib.sde_cv_wta_right, "sde_cv_wta_right", fl, fr, d0, d1, disp, min_cost, argmin, want, mode,
+                        workspace)
+
+
+def _cv_wta_view(fn, what, fl, fr, d0, d1, disp, min_cost, argmin, want, mode, workspace):
     pl, pr, H, W, C = _feat_pair(fl, fr)
     if "disp" in want and disp is None:
         disp = _empty((H, W), torch.float32, fl)
@@ -118,7 +133,7 @@ def cv_wta(fl, fr, d0: int, d1: int, disp=None, min_cost=None, argmin=None, want
         if workspace is None:
             workspace = torch.empty(need, dtype=torch.uint8, device=fl.device)
         pws, wsb = _need(workspace, "workspace", dtype=torch.uint8), workspace.numel()
-    check(lib.sde_cv_wta(pl, pr, H, W, C, int(d0), int(d1), pd, pm, pa, md, pws, wsb, _stream()), "sde_cv_wta")
+    check(fn(pl, pr, H, W, C, int(d0), int(d1), pd, pm, pa, md, pws, wsb, _stream()), what)
     return disp, min_cost, argmin
 
 
@@ -636,6 +651,23 @@ def lr_check(disp_l, disp_r, lrc_l=None, lrc_r=None):
     check(lib.sde_lr_check(_need(disp_l, "disp_l"), _need(disp_r, "disp_r", shape=(H, W)), H, W,
                            _need(lrc_l, "lrc_l", dtype=torch.uint8, shape=(H, W)),
                            _need(lrc_r, "lrc_r", dtype=torch.uint8, shape=(H, W)), _stream()), "sde_lr_check")
+    return lrc_l, lrc_r
+
+
+def lr_consistency(disp_l, disp_r, max_diff: float = 1.0, lrc_l=None, lrc_r=None):
+    """Left-right consistency flags without lr_check's uint8 column cast (sde_lr_consistency): a left pixel is
+    flagged when its disparity d is negative, or x - d is inside the row and |d - disp_r[y, int(x - d)]| >
+    max_diff; a right pixel likewise with x + d and disp_l.  Every pixel is written (the buffers need no
+    zeroing).  Returns (lrc_l, lrc_r) uint8 [H, W]."""
+    H, W = disp_l.shape
+    if lrc_l is None:
+        lrc_l = _empty((H, W), torch.uint8, disp_l)
+    if lrc_r is None:
+        lrc_r = _empty((H, W), torch.uint8, disp_l)
+    check(lib.sde_lr_consistency(_need(disp_l, "disp_l"), _need(disp_r, "disp_r", shape=(H, W)), H, W,
+                                 ctypes.c_float(max_diff), _need(lrc_l, "lrc_l", dtype=torch.uint8, shape=(H, W)),
+                                 _need(lrc_r, "lrc_r", dtype=torch.uint8, shape=(H, W)), _stream()),
+          "sde_lr_consistency")
     return lrc_l, lrc_r
 
 

@@ -6,6 +6,10 @@
     u8 images (HBM) -> z-norm + zero pad -> MC-CNN tower (x2) -> fused cost
     volume + WTA over [d0, d1)                         (configs 1/2, north star)
 
+optionally followed by the reference's post-processing on the two views' raw maps
+(``match_lr``): the right view of the fused kernel -> wrap-free LR check -> LRC
+fill -> 5x5 median,
+
 and the GPU path of ``disparity_compute_by_gpu`` (process_functional.py:1093-1267):
 
     features -> [H,W,D] L/R volumes -> penalties -> 8-path SGM (L, R) -> WTA
@@ -140,6 +144,7 @@ class StereoMatcher:
         self.split = [ops.new_split(H, W, dev) for _ in range(2)] \
             if (emit_split and cv_mode == "certified" and nlayers >= 2) else None
         self.split_valid = False
+        self.lr_bufs = None    # the right view and the checked path's maps, allocated on first use (_lr_bufs)
         self.sgm_bufs = None
         if sgm:
             self._alloc_sgm()
@@ -209,6 +214,59 @@ class StereoMatcher:
         self.features()
         self.cost_wta()
         return self.disp
+
+    # -- left-right-checked fast path ------------------------------------------
+    def _lr_bufs(self):
+        """The right view's outputs and workspace and the checked path's maps, allocated on first use: a matcher
+        that only runs match() never holds them."""
+        if self.lr_bufs is None:
+            H, W, dev = self.H, self.W, self.device
+            f32 = lambda: torch.empty((H, W), dtype=torch.float32, device=dev)   # noqa: E731
+            u8 = lambda: torch.empty((H, W), dtype=torch.uint8, device=dev)      # noqa: E731
+            self.disp_r, self.min_cost_r = f32(), f32()
+            self.argmin_r = torch.empty((H, W), dtype=torch.int32, device=dev)
+            self.cv_ws_r = torch.empty(ops.cv_wta_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+            self.lr_bufs = dict(lrc=[u8(), u8()], filled=f32(), checked=f32())
+        return self.lr_bufs
+
+    def cost_wta_right(self, want=("disp",)):
+        """The right view of cost_wta over this matcher's [d0, d1) (ops.cv_wta_right), into disp_r / min_cost_r /
+        argmin_r with its own workspace cv_ws_r.  Always reads the fp32 features (there is no right-view form
+        of the pre-split kernel)."""
+        self._lr_bufs()
+        return ops.cv_wta_right(self.feat[0], self.feat[1], self.d0, self.d1,
+                                disp=self.disp_r if "disp" in want else None,
+                                min_cost=self.min_cost_r if "min" in want else None,
+                                argmin=self.argmin_r if "argmin" in want else None, want=(),
+                                mode=self.cv_mode, workspace=self.cv_ws_r)
+
+    def _need_whole_range(self):
+        if (self.d0, self.d1) != (0, self.D):
+            raise ValueError(f"the left-right check needs both views over the whole range [0, {self.D}); this "
+                             f"matcher holds the shard [{self.d0}, {self.d1})")
+
+    def lr_checked(self, max_diff: float = 1.0):
+        """match_lr's stages after the features, on the features this matcher currently holds."""
+        self._need_whole_range()
+        b = self._lr_bufs()
+        self.cost_wta()
+        self.cost_wta_right()
+        ops.lr_consistency(self.disp, self.disp_r, max_diff, b["lrc"][0], b["lrc"][1])
+        ops.lrc_fill(self.disp, b["lrc"][0], out=b["filled"])
+        # the 5x5 median of the filled map into the interior of a copy of it: the 2-pixel border keeps the
+        # filled values
+        b["checked"].copy_(b["filled"])
+        ops.median5(b["filled"], b["checked"])
+        return b["checked"], self.disp_r, b["lrc"][0]
+
+    def match_lr(self, max_diff: float = 1.0):
+        """The hot path with the reference's post-processing (is_error_match / LRC / median,
+        process_functional.py:977-1088, :840-879) on both views' raw maps: features, cost_wta, cost_wta_right,
+        the wrap-free left-right check, LRC fill of the left map, 5x5 median.  Returns (disp_l_checked, disp_r,
+        lrc_l); self.disp keeps the raw left map.  Not for a disparity shard (ValueError)."""
+        self._need_whole_range()
+        self.features()
+        return self.lr_checked(max_diff)
 
     # -- GPU path of disparity_compute_by_gpu ---------------------------------
     def _place_sgm_volumes(self, pen, disp):
