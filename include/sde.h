@@ -436,6 +436,81 @@ int sde_lrc_fill(const float *disp_l, const uint8_t *lrc_l, int H, int W, float 
 /* Median_Filter_kernel (process_functional.py:840-879): 5x5 median of src into the interior of dst. */
 int sde_median5(const float *src, int H, int W, float *dst, void *stream);
 
+/* ---------------------------------------------------------------------- */
+/* Local matcher (local_mathod.py): SAD+SSD, rank and census.  It needs no   */
+/* weights: two uint8 images in, disparity maps out.  Additive in ABI 4.    */
+/* ---------------------------------------------------------------------- */
+/*
+ * Images are uint8 [H][W] (the reference reads cv2.IMREAD_GRAYSCALE and casts to float32: every value is an
+ * integer 0..255, so integer arithmetic reproduces its float arithmetic exactly); a pixel outside the image
+ * reads as 0.  Volumes are float32 [H][W][D] (SDE_LAYOUT_HWD, what sde_sgm_8path* takes), disparities
+ * float32 [H][W].  Limits of every entry point: H, W >= 1, 1 <= D <= 512; null or misordered arguments
+ * return SDE_ERR_ARG before any launch.
+ *
+ * SDE_LOCAL_INVALID: the float32 nearest the reference's literal 999999999999 (AD / Census_Cost fill,
+ * :49,150) = 999999995904, bits 0x5368d4a5.
+ *
+ * Census (Census_transform, :77-130): a 19-bit word built most-significant bit first --
+ *   for r in y-3..y-1 (outer), c in x-4..x-1 (inner): append I(r,c) > I(2y-r, 2x-c);
+ *   for r in y-3..y-1:                                append I(r,x) > I(2y-r, x);
+ *   for c in x-4..x-1:                                append I(y,c) > I(y, 2x-c).
+ * Not symmetric under a horizontal flip (the right view below cannot be built by flipping the images).
+ *
+ * Rank (Rank_transform, :51-75): the number of (r,c) in the 7x7 window around (y,x), centre included, with
+ * I(y,x) >= I(r,c): 1..49, stored as uint8.
+ *
+ * Hamming cost (Census_Cost, :132-150), left view:  L(y,x,d)  = popcount(cl[y][x] ^ cr[y][x-d]) for x-d >= 0,
+ * else `invalid`.  Right view (the standard construction, as sde_cost_volume's right side):
+ *                                                   R(y,x',d) = popcount(cl[y][x'+d] ^ cr[y][x']) for x'+d < W,
+ * else `invalid`; so R(y,x',d) == L(y,x'+d,d) on valid voxels.
+ *
+ * SAD+SSD cost (AD, :13-49), radius k (the script's -k), 0 <= k <= SDE_LOCAL_MAX_RADIUS:
+ *   e(r,c,d) = |l(r,c) - r_img(r,c-d)| + (l(r,c) - r_img(r,c-d))^2 as a signed integer;
+ *   rows max(y-k,0) .. min(y+k,H-1); columns by the reference's three branches:
+ *       x <  D+k                   [x,   x+k]
+ *       x >= D+k and x+k < W-k     [x-k, x+k]
+ *       otherwise                  [x-k, x]
+ *   cost(y,x,d) = float32(sum of e), rounded to nearest even from the exact integer, for x-d >= 0, else
+ *   `invalid` (Numba accumulates in float64, exact here, and stores float32: the same bits).  The first
+ *   branch reads column x+k, which the reference reads out of bounds when W < D+2k: the entry points
+ *   REQUIRE W >= D + 2k (SDE_ERR_ARG otherwise).  The largest sum is 65^2 * 65280 < 2^31.
+ *
+ * WTA (WTA__kernel, :152-165): best = c(0); for d = 1..D-1 take d if best > c(d) -- the first strict
+ * minimum, the rule of SDE_WTA_INIT_D0.  d = 0 is always valid and every real cost is below `invalid`, so
+ * the fused forms never return an invalid voxel and do not depend on `invalid`.
+ *
+ * Rank+SAD (the script's commented chain :203-204) is sde_ad_* on the two rank images, with the SIGNED
+ * difference.  The reference would subtract uint32 arrays there and Numba's unsigned arithmetic wraps; that
+ * wrap is not reproduced -- parity unpinned for this chain.
+ */
+#define SDE_LOCAL_MAX_RADIUS 32
+#define SDE_LOCAL_INVALID 999999995904.0f
+
+/* imgs: [nimg][H][W] (e.g. the left and right image back to back), census / rank: [nimg][H][W]. */
+int sde_census_transform(const uint8_t *imgs, int nimg, int H, int W, uint32_t *census, void *stream);
+int sde_rank_transform(const uint8_t *imgs, int nimg, int H, int W, uint8_t *rank, void *stream);
+
+/* The Hamming volumes; either output may be NULL, not both. */
+int sde_census_cost(const uint32_t *census_l, const uint32_t *census_r, int H, int W, int D, float invalid,
+                    float *out_left, float *out_right, void *stream);
+
+/*
+ * Hamming cost + WTA of both views in one pass, no volume written: disp_* the first minimum over d as float32,
+ * min_* (optional) the winner's cost as float32.  At least one of disp_l / disp_r; a view's min needs its disp.
+ * Equals sde_wta(sde_census_cost(...), SDE_LAYOUT_HWD, SDE_WTA_INIT_D0) per view.  H <= 65535.
+ */
+int sde_census_wta(const uint32_t *census_l, const uint32_t *census_r, int H, int W, int D, float *disp_l,
+                   float *min_l, float *disp_r, float *min_r, void *stream);
+
+/* The SAD+SSD volume (left view; the reference defines no right view for its one-sided windows). */
+int sde_ad_cost(const uint8_t *img_l, const uint8_t *img_r, int H, int W, int D, int radius, float invalid,
+                float *out_left, void *stream);
+
+/* SAD+SSD cost + WTA, no volume written: disp, and min_cost (optional) the winner's cost as float32.
+ * Equals sde_wta(sde_ad_cost(...), SDE_LAYOUT_HWD, SDE_WTA_INIT_D0).  H <= 4 * 65535. */
+int sde_ad_wta(const uint8_t *img_l, const uint8_t *img_r, int H, int W, int D, int radius, float *disp,
+               float *min_cost, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

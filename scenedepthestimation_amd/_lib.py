@@ -33,6 +33,8 @@ SDE_TOWER_IN_SPLIT, SDE_TOWER_OUT_SPLIT = 64, 128
 SDE_CV_EXACT, SDE_CV_CERTIFIED = 0, 1
 SDE_SGM_ACCUMULATE = 1
 SDE_SGM_ZERO_DU_PENALTIES = 2
+SDE_LOCAL_MAX_RADIUS = 32
+SDE_LOCAL_INVALID = 999999995904.0   # float32 nearest the reference's 999999999999 (bits 0x5368d4a5)
 
 # name -> (restype, argtypes); must cover every function declared in include/sde.h
 SIGNATURES = {
@@ -89,6 +91,13 @@ SIGNATURES = {
     "sde_lr_consistency": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "sde_lrc_fill": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sde_median5": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sde_census_transform": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sde_rank_transform": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sde_census_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "sde_census_wta": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
+    "sde_ad_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "sde_ad_wta": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -1,0 +1,162 @@
+"""The reference's classical local matcher (local_mathod.py) on the GPU: SAD+SSD, rank and census.
+
+    python -m scenedepthestimation_amd.local_method [-k 5] [--method ad|rank|census] [--ndisp 200]
+           [--lr-check] [--image-dir ./eval] [--out-dir ./result/SAD] [-n 5]
+
+It needs no weights: two grayscale images in, a disparity map out.  For pair i in 0..n-1 it reads
+``left_{i}.png`` / ``right_{i}.png`` from --image-dir and writes ``ld{i}.png`` as ``uint8(disparity)`` into
+--out-dir (local_mathod.py:172-211 hard-codes absolute paths; the defaults are their relative counterparts).
+
+  --method ad      AD + WTA__kernel, the chain the script runs (:201,208): the windowed SAD+SSD cost;
+  --method rank    Rank_transform + AD on the rank images (the commented chain :203-204).  Parity unpinned: the
+                   reference would subtract uint32 arrays there and Numba's unsigned arithmetic wraps; here the
+                   difference is signed;
+  --method census  Census_transform + Census_Cost (the commented chain :205-206): the Hamming cost.
+
+Every method runs the fused cost + WTA kernels (no volume is written).  --lr-check (census only: the reference
+defines no right view for the one-sided SAD windows) adds the right view from the same pass, the wrap-free
+left-right check, the LRC fill and the 5x5 median, composed as StereoMatcher.lr_checked does.  The SAD+SSD
+window needs W >= D + 2k: the reference reads column x + k out of bounds otherwise.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+METHODS = ("ad", "rank", "census")
+
+
+class LocalMatcher:
+    def __init__(self, height: int, width: int, ndisp: int = 200, method: str = "ad", radius: int = 5, device=None):
+        import torch
+
+        from . import ops
+        if method not in METHODS:
+            raise ValueError(f"method must be one of {METHODS}")
+        self.H, self.W, self.D, self.method, self.k = int(height), int(width), int(ndisp), method, int(radius)
+        if self.H < 1 or self.W < 1 or not 1 <= self.D <= 512:
+            raise ValueError("the local matcher needs H, W >= 1 and 1 <= ndisp <= 512")
+        if method != "census":
+            if not 0 <= self.k <= ops.LOCAL_MAX_RADIUS:
+                raise ValueError(f"radius must be in 0..{ops.LOCAL_MAX_RADIUS}")
+            if self.W < self.D + 2 * self.k:
+                raise ValueError(window_rule(self.W, self.D, self.k))
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        dev, H, W = self.device, self.H, self.W
+        # both images in one allocation: the transforms run the pair per launch
+        self.img_u82 = torch.empty((2, H, W), dtype=torch.uint8, device=dev)
+        self.disp = torch.empty((H, W), dtype=torch.float32, device=dev)
+        self.rank2 = torch.empty((2, H, W), dtype=torch.uint8, device=dev) if method == "rank" else None
+        self.census2 = torch.empty((2, H, W), dtype=torch.int32, device=dev) if method == "census" else None
+        self.lr_bufs = None    # the right view and the checked path's maps, allocated on first use (_lr_bufs)
+
+    def load_images(self, left_u8, right_u8):
+        """Host u8 [H,W] arrays (or device tensors) -> resident device images."""
+        import torch
+        for dst, src in zip(self.img_u82, (left_u8, right_u8)):
+            t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, np.uint8))
+            dst.copy_(t, non_blocking=False)
+
+    def match(self):
+        """The left disparity map the reference script computes for this method (float32 [H,W])."""
+        from . import ops
+        if self.method == "ad":
+            ops.ad_wta(self.img_u82[0], self.img_u82[1], self.D, self.k, disp=self.disp)
+        elif self.method == "rank":
+            ops.rank_transform(self.img_u82, out=self.rank2)
+            ops.ad_wta(self.rank2[0], self.rank2[1], self.D, self.k, disp=self.disp)
+        else:
+            ops.census_transform(self.img_u82, out=self.census2)
+            ops.census_wta(self.census2[0], self.census2[1], self.D, right=False, disp_l=self.disp)
+        return self.disp
+
+    def _lr_bufs(self):
+        if self.lr_bufs is None:
+            import torch
+            H, W, dev = self.H, self.W, self.device
+            f32 = lambda: torch.empty((H, W), dtype=torch.float32, device=dev)   # noqa: E731
+            u8 = lambda: torch.empty((H, W), dtype=torch.uint8, device=dev)      # noqa: E731
+            self.disp_r = f32()
+            self.lr_bufs = dict(lrc=[u8(), u8()], filled=f32(), checked=f32())
+        return self.lr_bufs
+
+    def match_lr(self, max_diff: float = 1.0):
+        """Census only: both views from one pass of the fused kernel, the wrap-free left-right check, the LRC
+        fill of the left map and the 5x5 median into the interior of a copy of the filled map (the 2-pixel
+        border keeps the filled values).  Returns (disp_l_checked, disp_r, lrc_l); self.disp keeps the raw left
+        map."""
+        from . import ops
+        if self.method != "census":
+            raise ValueError("match_lr needs method='census': the reference defines no right view for the "
+                             "one-sided SAD windows")
+        b = self._lr_bufs()
+        ops.census_transform(self.img_u82, out=self.census2)
+        ops.census_wta(self.census2[0], self.census2[1], self.D, disp_l=self.disp, disp_r=self.disp_r)
+        ops.lr_consistency(self.disp, self.disp_r, max_diff, b["lrc"][0], b["lrc"][1])
+        ops.lrc_fill(self.disp, b["lrc"][0], out=b["filled"])
+        b["checked"].copy_(b["filled"])
+        ops.median5(b["filled"], b["checked"])
+        return b["checked"], self.disp_r, b["lrc"][0]
+
+
+def window_rule(W, D, k):
+    return (f"the SAD+SSD window needs W >= D + 2k (got W = {W}, D = {D}, k = {k}): the reference reads column "
+            "x + k out of bounds otherwise")
+
+
+def build_parser():
+    p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                                description="local stereo matching method")
+    p.add_argument("-k", "--kernel", type=int, default=5, help="window size (the radius of the SAD+SSD window)")
+    p.add_argument("--method", choices=METHODS, default="ad", help="cost: SAD+SSD, SAD+SSD of the rank images, census")
+    p.add_argument("--ndisp", type=int, default=200, help="disparity range (the reference hard-codes 200)")
+    p.add_argument("--lr-check", action="store_true",
+                   help="with --method census: left-right check, LRC fill and 5x5 median on the two views")
+    p.add_argument("--image-dir", type=str, default="./eval", help="directory of left_{i}.png / right_{i}.png")
+    p.add_argument("--out-dir", type=str, default="./result/SAD", help="directory the ld{i}.png maps are written to")
+    p.add_argument("-n", "--num", type=int, default=5, help="number of pairs (the reference loops over 5)")
+    return p
+
+
+def parse_args(argv=None):
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.lr_check and args.method != "census":
+        p.error("--lr-check needs --method census (the reference defines no right view for the SAD windows)")
+    return args
+
+
+def run(args):
+    from . import imageio
+    paths = []
+    matcher = None
+    parser = build_parser()
+    for i in range(args.num):
+        lp = os.path.join(args.image_dir, "left_{}.png".format(i))
+        rp = os.path.join(args.image_dir, "right_{}.png".format(i))
+        left, right = imageio.imread_gray(lp), imageio.imread_gray(rp)
+        if left is None or right is None:
+            raise AttributeError(f"'NoneType' object has no attribute 'astype' (cannot read {lp} / {rp})")
+        H, W = left.shape
+        if args.method != "census" and W < args.ndisp + 2 * args.kernel:
+            parser.error(f"{lp}: " + window_rule(W, args.ndisp, args.kernel))
+        if matcher is None or (matcher.H, matcher.W) != (H, W):
+            matcher = LocalMatcher(H, W, args.ndisp, args.method, args.kernel)
+        matcher.load_images(left, right)
+        disp = matcher.match_lr()[0] if args.lr_check else matcher.match()
+        path = os.path.join(args.out_dir, "ld{}.png".format(i))
+        imageio.imwrite(path, disp.cpu().numpy().astype("uint8"))
+        paths.append(path)
+    return paths
+
+
+def main(argv=None):
+    for path in run(parse_args(argv)):
+        print(path, file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()

@@ -684,3 +684,134 @@ def median5(src, dst):
     H, W = src.shape
     check(lib.sde_median5(_need(src, "src"), H, W, _need(dst, "dst", shape=(H, W)), _stream()), "sde_median5")
     return dst
+
+
+# ----------------------------------------------------------------------------
+# Local matcher: SAD+SSD, rank and census (local_mathod.py:13-165; definitions in include/sde.h)
+# ----------------------------------------------------------------------------
+LOCAL_INVALID = _lib.SDE_LOCAL_INVALID
+LOCAL_MAX_RADIUS = _lib.SDE_LOCAL_MAX_RADIUS
+
+
+def _images(imgs, name="images"):
+    """u8 [H,W] or [N,H,W] -> (pointer, N, H, W)."""
+    if not isinstance(imgs, torch.Tensor) or imgs.dim() not in (2, 3):
+        raise ValueError(f"{name} must be a uint8 [H,W] or [N,H,W] tensor")
+    p = _need(imgs, name, dtype=torch.uint8)
+    H, W = imgs.shape[-2:]
+    return p, (imgs.shape[0] if imgs.dim() == 3 else 1), H, W
+
+
+def census_transform(imgs, out=None):
+    """u8 [H,W] or [N,H,W] -> the 19-bit census words as int32 of the same shape (sde_census_transform)."""
+    p, N, H, W = _images(imgs)
+    if out is None:
+        out = _empty(tuple(imgs.shape), torch.int32, imgs)
+    check(lib.sde_census_transform(p, N, H, W, _need(out, "census", dtype=torch.int32, shape=tuple(imgs.shape)),
+                                   _stream()), "sde_census_transform")
+    return out
+
+
+def rank_transform(imgs, out=None):
+    """u8 [H,W] or [N,H,W] -> the 7x7 rank (1..49) as uint8 of the same shape (sde_rank_transform)."""
+    p, N, H, W = _images(imgs)
+    if out is None:
+        out = _empty(tuple(imgs.shape), torch.uint8, imgs)
+    check(lib.sde_rank_transform(p, N, H, W, _need(out, "rank", dtype=torch.uint8, shape=tuple(imgs.shape)),
+                                 _stream()), "sde_rank_transform")
+    return out
+
+
+def _census_pair(census_l, census_r):
+    if not isinstance(census_l, torch.Tensor) or census_l.dim() != 2:
+        raise ValueError("census words must be int32 [H,W] tensors")
+    H, W = census_l.shape
+    return (_need(census_l, "census_l", dtype=torch.int32), _need(census_r, "census_r", dtype=torch.int32, shape=(H, W)),
+            H, W)
+
+
+def census_cost(census_l, census_r, ndisp: int, invalid: float = LOCAL_INVALID, left: bool = True,
+                right: bool = False, out_left=None, out_right=None):
+    """The Hamming volumes f32 [H,W,D] (sde_census_cost): the left one, (left, right) with right=True, the
+    right one alone with left=False."""
+    pl, pr, H, W = _census_pair(census_l, census_r)
+    if not left and not right:
+        raise ValueError("nothing to compute")
+    shape = (H, W, int(ndisp))
+    ol = orr = None
+    if left:
+        if out_left is None:
+            out_left = _empty(shape, torch.float32, census_l)
+        ol = _need(out_left, "out_left", shape=shape)
+    if right:
+        if out_right is None:
+            out_right = _empty(shape, torch.float32, census_l)
+        orr = _need(out_right, "out_right", shape=shape)
+    check(lib.sde_census_cost(pl, pr, H, W, int(ndisp), ctypes.c_float(invalid), ol, orr, _stream()),
+          "sde_census_cost")
+    if not left:
+        return out_right
+    return (out_left, out_right) if right else out_left
+
+
+def census_wta(census_l, census_r, ndisp: int, left: bool = True, right: bool = True, want_min: bool = False,
+               disp_l=None, min_l=None, disp_r=None, min_r=None):
+    """Hamming cost + first-minimum WTA of both views in one pass, no volume (sde_census_wta).
+    Returns (disp_l, min_l, disp_r, min_r); the entries not asked for are None."""
+    pl, pr, H, W = _census_pair(census_l, census_r)
+    if not left and not right:
+        raise ValueError("nothing to compute")
+
+    def view(on, disp, mn):
+        if not on:
+            return None, None
+        if disp is None:
+            disp = _empty((H, W), torch.float32, census_l)
+        if want_min and mn is None:
+            mn = _empty((H, W), torch.float32, census_l)
+        return disp, mn
+
+    disp_l, min_l = view(left, disp_l, min_l)
+    disp_r, min_r = view(right, disp_r, min_r)
+    ptr = lambda t, n: _need(t, n, shape=(H, W)) if t is not None else None   # noqa: E731
+    check(lib.sde_census_wta(pl, pr, H, W, int(ndisp), ptr(disp_l, "disp_l"), ptr(min_l, "min_l"),
+                             ptr(disp_r, "disp_r"), ptr(min_r, "min_r"), _stream()), "sde_census_wta")
+    return disp_l, min_l, disp_r, min_r
+
+
+def _image_pair(img_l, img_r):
+    if not isinstance(img_l, torch.Tensor) or img_l.dim() != 2:
+        raise ValueError("images must be uint8 [H,W] tensors")
+    H, W = img_l.shape
+    return _need(img_l, "img_l", dtype=torch.uint8), _need(img_r, "img_r", dtype=torch.uint8, shape=(H, W)), H, W
+
+
+def _ad_rule(W, ndisp, radius):
+    if W < ndisp + 2 * radius:
+        raise ValueError(f"the SAD+SSD window needs W >= D + 2k (got W = {W}, D = {ndisp}, k = {radius}): the "
+                         "reference reads column x + k out of bounds otherwise")
+
+
+def ad_cost(img_l, img_r, ndisp: int, radius: int, invalid: float = LOCAL_INVALID, out=None):
+    """The SAD+SSD volume f32 [H,W,D] of two u8 images (sde_ad_cost); W >= D + 2 * radius."""
+    pl, pr, H, W = _image_pair(img_l, img_r)
+    _ad_rule(W, int(ndisp), int(radius))
+    if out is None:
+        out = _empty((H, W, int(ndisp)), torch.float32, img_l)
+    check(lib.sde_ad_cost(pl, pr, H, W, int(ndisp), int(radius), ctypes.c_float(invalid),
+                          _need(out, "out", shape=(H, W, int(ndisp))), _stream()), "sde_ad_cost")
+    return out
+
+
+def ad_wta(img_l, img_r, ndisp: int, radius: int, want_min: bool = False, disp=None, min_cost=None):
+    """SAD+SSD cost + first-minimum WTA, no volume (sde_ad_wta).  Returns (disp, min_cost or None)."""
+    pl, pr, H, W = _image_pair(img_l, img_r)
+    _ad_rule(W, int(ndisp), int(radius))
+    if disp is None:
+        disp = _empty((H, W), torch.float32, img_l)
+    if want_min and min_cost is None:
+        min_cost = _empty((H, W), torch.float32, img_l)
+    pm = _need(min_cost, "min_cost", shape=(H, W)) if min_cost is not None else None
+    check(lib.sde_ad_wta(pl, pr, H, W, int(ndisp), int(radius), _need(disp, "disp", shape=(H, W)), pm, _stream()),
+          "sde_ad_wta")
+    return disp, min_cost
