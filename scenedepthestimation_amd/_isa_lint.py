@@ -33,7 +33,7 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 STORE_DATA_WINDOW = 2
 MFMA_STORE_DATA_WINDOW = 9
 TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
-HOST_ONLY = {"tower_pack.o"}   # objects of sources without kernels (csrc/tower_pack.hip): nothing to lint
+HOST_ONLY = {"tower_pack.o", "sde_abi.o"}   # objects of sources without kernels (csrc/tower_pack.hip, sde_abi.hip): nothing to lint
 
 _WIDE_STORE = re.compile(r"^(buffer|global|flat|scratch)_store_(dwordx3|dwordx4|format_xyz|format_xyzw|b96|b128)\b")
 _FUNC = re.compile(r"^[0-9a-f]+ <(.+)>:$")

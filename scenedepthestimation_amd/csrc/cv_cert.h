@@ -1,8 +1,20 @@
-// cv_cert.h -- shared pieces of the certified fused cost volume + WTA (cost_volume.hip, cv_row.hip).
+// cv_cert.h -- the certificate of the fused cost volume + WTA (north-star kernel) and what its two sweeps
+// share: the row sweep (cv_row.hip) and the pre-split tile path (cv_tile.h).
 //
-// Scores s(x,d) = fl[x] . fr[x-d] on the bf16 MFMA with every fp32 operand split
-// into hi + lo bf16 parts; see cost_volume.hip for the error bound (FX_K) that
-// certifies a fast argmax as the exact first-min.
+// Scores s(x,d) = fl[x] . fr[x-d] are computed on the bf16 MFMA (v_mfma_f32_32x32x16_bf16; the row sweep uses
+// fp16 parts and its own, tighter constant: see cv_row.hip) with every fp32 operand split into hi + lo parts and
+// the three leading partial products (hh, hl, lh) accumulated in fp32.  Rigorous bound for every voxel of a
+// pixel (Cauchy-Schwarz on |a|,|b|):
+//   |s_fast - s_true| <= (3*2^-16 + 192*2^-23) * sum|a_c b_c|   (split + accumulation)
+//   |s_exact - s_true| <= 10*2^-24 * sum|a_c b_c|               (NumPy pairwise order)
+//   => |s_fast - s_exact| <= FX_K * sum|a_c b_c| <= FX_K * ||fl[x]||_2 * max_window ||fr||_2
+//      (FX_K = 1e-4: 1.4x margin over 7e-5; the per-pixel L2 norms are fp32 sums of
+//      squares inflated by FX_NORM_UP = 1 + 4e-6, an upper bound)
+// If the best fast score beats the runner-up by more than 2 eps, the exact first-min is provably the fast
+// argmax (no other d can tie or win exactly), and its exact cost is computed once (same arithmetic as
+// cv64_kernel, cv_exact.h).  Any other pixel (near-ties, NaN/Inf features) goes to a work list that
+// cv_wta_fixup_kernel (cv_wta.hip) resolves with the exact scan.  Outputs are therefore bit-identical to
+// the exact kernel for every input.
 #pragma once
 
 #include "sde_common.h"
@@ -13,56 +25,11 @@ typedef __bf16 fx_bf16x8 __attribute__((ext_vector_type(8)));
 typedef float fx_floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int FX_NX = 64;          // left pixels per workgroup
-constexpr int FX_DCH = 128;        // disparities per window chunk
-constexpr int FX_NT = 6;           // max M-tiles per chunk: ceil((128 + 63) / 32)
-constexpr int FX_WIN = FX_NT * 32; // window pixels
 constexpr float FX_K = 1e-4f;
 constexpr float FX_ABS = 1e-30f;   // absolute slack (bf16 subnormal handling)
-
-// Exact NumPy-order cost of two 64-float rows in global memory (16-B loads).
-__device__ __forceinline__ float dot64_exact_global(const float4 *__restrict__ a, const float4 *__restrict__ b)
-{
-    float acc[8];
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-        const float4 a0 = a[2 * m], a1 = a[2 * m + 1], b0 = b[2 * m], b1 = b[2 * m + 1];
-        const float p[8] = {a0.x * b0.x, a0.y * b0.y, a0.z * b0.z, a0.w * b0.w,
-                            a1.x * b1.x, a1.y * b1.y, a1.z * b1.z, a1.w * b1.w};
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) acc[jj] = (m == 0) ? p[jj] : acc[jj] + p[jj];
-    }
-    const float res = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-    return -(0.0f + res);
-}
-
-// the same bits with at most two 32-byte steps of loads in flight (for kernels at tight VGPR budgets)
-__device__ __forceinline__ float dot64_exact_global_lean(const float4 *__restrict__ a, const float4 *__restrict__ b)
-{
-    float acc[8];
-    {
-        const float4 a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
-        acc[0] = a0.x * b0.x; acc[1] = a0.y * b0.y; acc[2] = a0.z * b0.z; acc[3] = a0.w * b0.w;
-        acc[4] = a1.x * b1.x; acc[5] = a1.y * b1.y; acc[6] = a1.z * b1.z; acc[7] = a1.w * b1.w;
-    }
-#pragma unroll 1
-    for (int m = 1; m < 8; m++) {
-        const float4 a0 = a[2 * m], a1 = a[2 * m + 1], b0 = b[2 * m], b1 = b[2 * m + 1];
-        const float p[8] = {a0.x * b0.x, a0.y * b0.y, a0.z * b0.z, a0.w * b0.w,
-                            a1.x * b1.x, a1.y * b1.y, a1.z * b1.z, a1.w * b1.w};
-#pragma unroll
-        for (int jj = 0; jj < 8; jj++) acc[jj] = acc[jj] + p[jj];
-    }
-    const float res = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-    return -(0.0f + res);
-}
+constexpr float FX_NORM_UP = 1.000004f;
 
 __device__ __forceinline__ int fx_slot(int r, int c8) { return r * 8 + (c8 ^ ((r >> 1) & 7)); }
-
-__device__ __forceinline__ void fx_split(float x, __bf16 &h, __bf16 &l)
-{
-    h = (__bf16)x;
-    l = (__bf16)(x - (float)h);
-}
 
 // merge (best, arg, second) of two disjoint candidate sets, scores in max-domain
 __device__ __forceinline__ void fx_merge(float &b, int &a, float &s, float b2, int a2, float s2)
@@ -71,15 +38,6 @@ __device__ __forceinline__ void fx_merge(float &b, int &a, float &s, float b2, i
     if (b2 > b || (b2 == b && a2 < a)) { b = b2; a = a2; }
     s = ns;
 }
-
-__device__ __forceinline__ int xcd_remap(int b, int nb)
-{
-    // bijective: blocks b, b+8, ... (one XCD under round-robin dispatch) get consecutive logical ids
-    const int q = nb / 8, r = nb % 8, x = b % 8;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
-}
-
-constexpr float FX_NORM_UP = 1.000004f;
 
 // the row-sweep kernel (cv_row.hip): window size limit and launcher (mirror: the right view)
 bool row_cert_supported(int d0, int d1);

@@ -2,7 +2,7 @@
 //
 // Replaces (WHDY/SceneDepthEstimation) compute_cost_volume + WTA1,
 // process_functional.py:48-73 + 96-113, fused: the disparity map is bit-identical
-// to WTA1(compute_cost_volume(fl, fr, D)) (see cv_cert.h / cost_volume.hip for the
+// to WTA1(compute_cost_volume(fl, fr, D)) (see cv_cert.h for the
 // certificate).  Built with -fno-honor-nans -mno-amdgpu-ieee (see _build.py): the
 // per-score max / median / compare run without NaN canonicalisation, so every
 // decision that must survive non-finite input is taken on integer bit tests.
@@ -34,7 +34,7 @@ namespace sde {
 // k-1 retired, so one barrier per superstrip orders both directions.  Tiles left of the image are
 // zero-filled, so an invalid voxel (x < d) scores exactly +0 = -(-0.0), like the CPU path.
 //
-// Per pixel, the certificate of cv_wta_cert_kernel (cost_volume.hip) with the bound below: if the
+// Per pixel, the certificate of cv_cert.h with the bound below: if the
 // best fast score beats the runner-up by more than 2 eps, the fast argmax is the exact first
 // minimum, and its exact cost is recomputed from the fp32 rows (L2-resident) when requested; every
 // other pixel goes to the fix-up list.  Outputs are bit-identical to the exact kernel.
@@ -50,14 +50,14 @@ namespace sde {
 // the mirrored pair; the bound below is symmetric in its two operands (RW_K |a| |b| + RW_ABS (|a| + |b|)), so no
 // constant changes.
 // ---------------------------------------------------------------------------
-// Arithmetic of the fast scores and their bound (the chunked kernels of cost_volume.hip use bf16
+// Arithmetic of the fast scores and their bound (the pre-split tile kernel of cv_tile.h uses bf16
 // hi/lo instead): every operand is scaled by 2^RW_S (exact) and split into two fp16 parts, x*2^S =
 // h + l + r; the three partial products run on v_mfma_f32_32x32x16_f16, the eight small-term MFMAs
 // (l*h', h*l') of a tile before the four leading ones (h*h').  Bound per voxel (a = fl[x],
-// b = fr[x-d], Cauchy-Schwarz as in cost_volume.hip):
+// b = fr[x-d], Cauchy-Schwarz as in cv_cert.h):
 //   split: |r| <= 2^-22 |x| 2^S (fp16 11-bit parts) and the dropped l*l' <= 2^-22 |ab| 2^2S
 //          -> 3.001 * 2^-22 * sum|ab|                                         (7.2e-7)
-//   accumulation, the conservative per-add model of cost_volume.hip (2^-23 of the running
+//   accumulation, the conservative per-add model of cv_cert.h (2^-23 of the running
 //   sum per product): 128 small-term adds on partial sums <= 2.002 * 2^-11 sum|ab|, then 64
 //   leading adds on partial sums <= 1.002 sum|ab|  -> (64 * 1.002 + 0.13) * 2^-23  (7.7e-6)
 //   NumPy pairwise order of the exact cost: 10 * 2^-24                        (6.0e-7)
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                 // barrier: lane (j, h) forms dot64_exact_global's partial sums acc[4h .. 4h+3] (channels 8m + 4h ..
                 // 8m + 4h + 3 = float4 2m + h of each operand, all 16 loads in flight) and its half of the final tree,
                 // ((acc0 + acc1) + (acc2 + acc3)) or ((acc4 + acc5) + (acc6 + acc7)); a permlane32 swap adds the
-                // halves in that order: the same bits, one round of loads instead of dot64_exact_global_lean's eight
+                // halves in that order: the same bits as that function's (cv_exact.h), in one round of loads
                 const uint32_t lo_arg = __builtin_amdgcn_permlane32_swap((uint32_t)arg, (uint32_t)arg, false, false)[0];
                 const int ab = h ? (int)lo_arg : arg;   // the upper half takes lane j's merged arg
                 const int xr = x - ab;

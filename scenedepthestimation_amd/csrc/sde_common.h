@@ -60,10 +60,13 @@ static inline void launch_lds(dim3 grid, dim3 block, hipStream_t st, Args... arg
     hipLaunchKernelGGL(K, grid, block, SMEM, st, args...);
 }
 
-// 64-float (256 B) rows in LDS, XOR-swizzled at 16-B granularity: the 16 lanes
-// of one ds_read_b128 group that read the same logical chunk of 16 consecutive
-// rows land on 16 distinct 16-B slots of the 256-B bank row (conflict-free).
-__device__ __forceinline__ int swz_row16(int row, int chunk) { return row * 16 + (chunk ^ (row & 15)); }
+// Logical id of block b of nb, so that the blocks one XCD runs share its L2 on neighbouring work.
+__device__ __forceinline__ int xcd_remap(int b, int nb)
+{
+    // bijective: blocks b, b+8, ... (one XCD under round-robin dispatch) get consecutive logical ids
+    const int q = nb / 8, r = nb % 8, x = b % 8;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + b / 8;
+}
 
 // NumPy float32 pairwise sum of elementwise products, 0.0f + pairwise(a*b)
 // (numpy loops_utils.h.src pairwise_sum; add.reduce identity 0.0).  Products

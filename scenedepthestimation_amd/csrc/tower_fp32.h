@@ -43,7 +43,7 @@ __device__ __forceinline__ void store_tap(float2 *wt, const float4 (&r)[2])
     }
 }
 
-// Last-layer extras for the certified cost volume (see cost_volume.hip):
+// Last-layer extras for the certified cost volume (see cv_tile.h):
 // bf16 hi/lo split planes of the output features (x = hi + lo + r, RNE) and
 // an upper bound of each pixel's L2 norm.  A lane holds channels
 // mt*32 + 8g + 4h + e (e = 0..3) of its pixel in v[mt][4g + e].

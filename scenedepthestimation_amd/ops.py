@@ -115,8 +115,10 @@ def cv_wta_right(fl, fr, d0: int, d1: int, disp=None, min_cost=None, argmin=None
                         workspace)
 
 
-def _cv_wta_view(fn, what, fl, fr, d0, d1, disp, min_cost, argmin, want, mode, workspace):
-    pl, pr, H, W, C = _feat_pair(fl, fr)
+def _wta_outputs(fl, H, W, want, disp, min_cost, argmin):
+    """The (disp, min_cost, argmin) maps of a fused CV + WTA call and their pointers: those named in `want` are
+    allocated on fl's device unless given; every one given is validated, and an output neither wanted nor given
+    stays None (a null pointer: the kernel skips it)."""
     if "disp" in want and disp is None:
         disp = _empty((H, W), torch.float32, fl)
     if "min" in want and min_cost is None:
@@ -126,6 +128,12 @@ def _cv_wta_view(fn, what, fl, fr, d0, d1, disp, min_cost, argmin, want, mode, w
     pd = _need(disp, "disp", shape=(H, W)) if disp is not None else None
     pm = _need(min_cost, "min_cost", shape=(H, W)) if min_cost is not None else None
     pa = _need(argmin, "argmin", dtype=torch.int32, shape=(H, W)) if argmin is not None else None
+    return (disp, min_cost, argmin), (pd, pm, pa)
+
+
+def _cv_wta_view(fn, what, fl, fr, d0, d1, disp, min_cost, argmin, want, mode, workspace):
+    pl, pr, H, W, C = _feat_pair(fl, fr)
+    (disp, min_cost, argmin), (pd, pm, pa) = _wta_outputs(fl, H, W, want, disp, min_cost, argmin)
     md = CV_MODES[mode]
     pws, wsb = None, 0
     if md == _lib.SDE_CV_CERTIFIED:
@@ -145,15 +153,7 @@ def cv_wta_split(fl, fr, split_l, split_r, d0: int, d1: int, disp=None, min_cost
                  workspace=None, want=("disp",)):
     """Certified fused CV + WTA on pre-split operands (tower-emitted or feature_split)."""
     pl, pr, H, W, C = _feat_pair(fl, fr)
-    if "disp" in want and disp is None:
-        disp = _empty((H, W), torch.float32, fl)
-    if "min" in want and min_cost is None:
-        min_cost = _empty((H, W), torch.float32, fl)
-    if "argmin" in want and argmin is None:
-        argmin = _empty((H, W), torch.int32, fl)
-    pd = _need(disp, "disp", shape=(H, W)) if disp is not None else None
-    pm = _need(min_cost, "min_cost", shape=(H, W)) if min_cost is not None else None
-    pa = _need(argmin, "argmin", dtype=torch.int32, shape=(H, W)) if argmin is not None else None
+    (disp, min_cost, argmin), (pd, pm, pa) = _wta_outputs(fl, H, W, want, disp, min_cost, argmin)
     if workspace is None:
         workspace = torch.empty(cv_wta_split_workspace_bytes(H, W), dtype=torch.uint8, device=fl.device)
     lh, ll, ln = _split_ptrs(split_l, (H, W))

@@ -16,7 +16,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "scenedepthestimation_amd", "csrc")
 SLACK = 64          # pixels of window slack per side: one 32-pixel tile + one 32-pixel group
-ROW_CHUNK = 256     # disparities per launch of the chunked row sweep (cost_volume.hip)
+ROW_CHUNK = 256     # disparities per launch of the chunked row sweep (cv_wta.hip)
 
 
 def _const(text, name):

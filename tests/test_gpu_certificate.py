@@ -28,7 +28,7 @@ def host(t):
 
 def fixup_list(ws):
     """The pixels a single row sweep, or the split path's kernel, sent to the exact fix-up: the workspace's
-    word 0 counts them, their int32 indices y W + x start at byte 256 (cost_volume.hip, the certified-mode
+    word 0 counts them, their int32 indices y W + x start at byte 256 (cv_wta.hip, the certified-mode
     workspace).  (The chunked path reuses the list per chunk: only its counts remain.)"""
     torch.cuda.synchronize()
     n = int(ws[:4].view(torch.int32).item())

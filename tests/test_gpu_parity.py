@@ -166,6 +166,30 @@ def test_generic_channel_counts(gpu, golden, golden_cases):
         assert np.array_equal(host(disp), golden[n + "__disp"]), n
 
 
+@pytest.mark.parametrize("H,W,D", [(2, 37, 9), (1, 5, 9)])
+@pytest.mark.parametrize("C", [5, 24, 130])
+def test_generic_hwd_volumes_vs_oracle(gpu, oracle, C, H, W, D):
+    """C != 64 in the [H,W,D] layout (cv_generic_kernel<OUT_HWD>): both volumes together, the left alone and the
+    right alone, byte-equal to the oracle.  C = 5 is below one 8-block, 24 the <= 128 loop, 130 the recursion;
+    W is no multiple of anything and (1, 5, 9) has D > W.  NaN-filled outputs catch any voxel left unwritten."""
+    from scenedepthestimation_amd import ops
+    rng = np.random.default_rng(1000 * C + W)
+    fl = l2n(rng.standard_normal((H, W, C)).astype(np.float32))
+    fr = l2n(rng.standard_normal((H, W, C)).astype(np.float32))
+    oL, oR = oracle.cost_volume_hwd(fl, fr, D, invalid=1.0)
+
+    def nan():
+        return torch.full((H, W, D), float("nan"), device="cuda")
+    L, R, L1, R1 = nan(), nan(), nan(), nan()
+    ops.cost_volume(dev(fl), dev(fr), D, layout="HWD", right=True, invalid=1.0, out_left=L, out_right=R)
+    assert host(L).tobytes() == oL.tobytes()
+    assert host(R).tobytes() == oR.tobytes()
+    ops.cost_volume(dev(fl), dev(fr), D, layout="HWD", invalid=1.0, out_left=L1)
+    assert host(L1).tobytes() == oL.tobytes()
+    ops.cost_volume(dev(fl), dev(fr), D, layout="HWD", right=True, left=False, invalid=1.0, out_right=R1)
+    assert host(R1).tobytes() == oR.tobytes()
+
+
 # ----------------------------------------------------------------------------
 # tower
 # ----------------------------------------------------------------------------

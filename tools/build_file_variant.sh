@@ -5,6 +5,10 @@
 # tower.hip -DSDE_SPLIT_ACT=1; tower_x6p.hip, tower_wino.hip and tower_fp32.hip hold the other families.
 # An SGM variant rebuilds sgm.hip (it includes sgm_scan.h, sgm_faithful.h and sgm_wave.h): ... sgm.hip sgm_NAME;
 # the post-processing kernels are postprocess.hip.
+# The cost volume is one file per concern: a cvlr3_kernel variant (cv_lr.h) rebuilds cv_volume.hip; a fix-up, tile-path
+# (cv_tile.h) or chunk-merge variant rebuilds cv_wta.hip; the exact kernels (cv_exact.h) are in both objects: rebuild
+# the one whose entry point is timed; the row sweep is cv_row.hip (its two extra flags are added below); sde_wta's
+# kernels are wta.hip.
 set -e
 cd "$(dirname "$0")/.."
 F=$1; NAME=$2; shift 2
