@@ -511,6 +511,52 @@ int sde_ad_cost(const uint8_t *img_l, const uint8_t *img_r, int H, int W, int D,
 int sde_ad_wta(const uint8_t *img_l, const uint8_t *img_r, int H, int W, int D, int radius, float *disp,
                float *min_cost, void *stream);
 
+/* ---------------------------------------------------------------------- */
+/* Training of the MC-CNN-fast branch (train.py:71-99, mc_cnn_brunch.py:31-48):  */
+/* hinge loss over (left, positive, negative) patch triplets, momentum SGD.    */
+/* Additive in ABI 4.                                                       */
+/* ---------------------------------------------------------------------- */
+/*
+ * Limits of every entry point: nf == 64, 1 <= nlayers <= 5, B >= 1 and 3*B*P*P*64 < 2^31 with the patch side
+ * P = 2*nlayers + 1 (32-bit offsets); anything else, a null pointer or a short workspace returns SDE_ERR_ARG
+ * before any launch (the size queries return -1).  fp32 storage, fp32 FMA accumulation.
+ *
+ * Parameter blob (also the layout of gradients and momentum velocity): float32, the reference's variable order
+ * and HWIO layout -- w1 [3][3][1][nf], b1 [nf], w2 [3][3][nf][nf], b2 [nf], ...
+ *
+ * Definition.  N = 3B patches, left / positive / negative back to back, each through the same tower:
+ *   conv        out[y][x][co] = b[co] + sum in[y+ky][x+kx][ci] * w[ky][kx][ci][co]   (VALID), ReLU on all but the last
+ *   normalise   y = x * r,  r = 1/sqrt(max(sum x^2, 1e-12))
+ *   h_i = margin - (l_i.p_i - l_i.n_i),  loss = mean_i max(0, h_i)
+ * and backward: ReLU gradient [z > 0]; normalise dx = r * (g - y * (y.g)) where sum x^2 >= 1e-12, else 1e6 * g;
+ * a_i = [h_i > 0] / B, dl_i = a_i * (n_i - p_i), dp_i = -a_i * l_i, dn_i = a_i * l_i; weight and bias
+ * gradients summed over all 3B patches.  No floating-point atomics and a reduction order that depends on the
+ * shape alone: the same inputs give the same bytes.
+ */
+int64_t sde_train_param_floats(int nlayers, int nf);
+int64_t sde_train_workspace_bytes(int B, int nlayers, int nf);
+
+/* img_l / img_r: float32 [H][W] normalised images; idx: int32 [B][4] = (y, x_left, x_pos, x_neg) patch centres;
+ * patches: float32 [3][B][P][P] (left, positive, negative).  A pixel outside the image reads 0 (the tower's
+ * zero padding). */
+int sde_train_gather(const float *img_l, const float *img_r, int H, int W, const int32_t *idx, int B, int nlayers,
+                     float *patches, void *stream);
+
+/* Forward + backward.  loss: float32 [1 + B] = the mean, then every h_i.  grads: the blob layout, every element
+ * written; NULL = forward only.  ws: sde_train_workspace_bytes(B, nlayers, nf), 16-byte aligned like params (SDE_ERR_ARG otherwise);
+ * it keeps the activations for sde_train_export_activations. */
+int sde_train_loss_grad(const float *patches, int B, const float *params, int nlayers, int nf, float margin,
+                        float *loss, float *grads, void *ws, int64_t ws_bytes, void *stream);
+
+/* Copy what the last sde_train_loss_grad on ws kept for `layer` (1-based) to out [3B][h][w][nf]: the post-ReLU
+ * output of a layer < nlayers (h = w = P - 2*layer), the normalised features [3B][nf] for layer == nlayers. */
+int sde_train_export_activations(const void *ws, int B, int nlayers, int nf, int layer, float *out, void *stream);
+
+/* TF's MomentumOptimizer (non-Nesterov), one fp32 rounding per operation:
+ * v = fl(fl(beta * v) + g); p = fl(p - fl(lr * v)).  n floats each. */
+int sde_train_momentum(float *params, float *velocity, const float *grads, int64_t n, float lr, float beta,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,6 +9,8 @@ Submodules
                      disparity_compute_by_gpu)
   parallel           multi-GPU: pair data-parallel and disparity-sharded cost volume + RCCL all-gather
   match_single, match  the reference's CLI entry points
+  training, train    Trainer / TripletSampler / PatchFileDataset and the reference's training CLI
+  pfm                PFM reader / writer of the training patch files
 """
 __version__ = "0.1.0"
 

@@ -98,6 +98,13 @@ SIGNATURES = {
                                c_void_p]),
     "sde_ad_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "sde_ad_wta": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sde_train_param_floats": (c_int64, [c_int, c_int]),
+    "sde_train_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "sde_train_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sde_train_loss_grad": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_void_p]),
+    "sde_train_export_activations": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sde_train_momentum": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
 }
 
 

@@ -815,3 +815,82 @@ def ad_wta(img_l, img_r, ndisp: int, radius: int, want_min: bool = False, disp=N
     check(lib.sde_ad_wta(pl, pr, H, W, int(ndisp), int(radius), _need(disp, "disp", shape=(H, W)), pm, _stream()),
           "sde_ad_wta")
     return disp, min_cost
+
+
+# ----------------------------------------------------------------------------
+# training step (train.py:71-99): gather, loss + gradients, momentum update
+# ----------------------------------------------------------------------------
+def train_param_floats(nlayers: int, nf: int = 64) -> int:
+    n = lib.sde_train_param_floats(int(nlayers), int(nf))
+    if n < 0:
+        raise ValueError(f"unsupported training shape nlayers={nlayers} nf={nf}")
+    return int(n)
+
+
+def train_workspace_bytes(B: int, nlayers: int, nf: int = 64) -> int:
+    n = lib.sde_train_workspace_bytes(int(B), int(nlayers), int(nf))
+    if n < 0:
+        raise ValueError(f"unsupported training shape B={B} nlayers={nlayers} nf={nf}")
+    return int(n)
+
+
+def train_gather(img_l, img_r, idx, nlayers: int, out=None):
+    """f32 [H,W] normalised images + int32 [B,4] centres (y, x_left, x_pos, x_neg) -> patches f32 [3,B,P,P]
+    (sde_train_gather); pixels outside the image read 0."""
+    if img_l.dim() != 2 or tuple(img_l.shape) != tuple(img_r.shape):
+        raise ValueError(f"images must be matching [H,W] tensors, got {tuple(img_l.shape)} / {tuple(img_r.shape)}")
+    H, W = img_l.shape
+    if idx.dim() != 2 or idx.shape[1] != 4:
+        raise ValueError(f"idx must be [B,4], got {tuple(idx.shape)}")
+    B, P = idx.shape[0], 2 * int(nlayers) + 1
+    if out is None:
+        out = _empty((3, B, P, P), torch.float32, img_l)
+    check(lib.sde_train_gather(_need(img_l, "img_l"), _need(img_r, "img_r"), H, W,
+                               _need(idx, "idx", dtype=torch.int32), B, int(nlayers),
+                               _need(out, "patches", shape=(3, B, P, P)), _stream()), "sde_train_gather")
+    return out
+
+
+def train_loss_grad(patches, params, nlayers: int, margin: float, loss=None, grads=None, workspace=None,
+                    nf: int = 64, want_grads: bool = True):
+    """patches f32 [3,B,P,P], params f32 blob -> (loss f32 [1+B] = mean then every h_i, grads blob or None)
+    (sde_train_loss_grad).  want_grads=False runs the forward pass only."""
+    P = 2 * int(nlayers) + 1
+    if patches.dim() != 4 or patches.shape[0] != 3:
+        raise ValueError(f"patches must be [3,B,{P},{P}], got {tuple(patches.shape)}")
+    B = patches.shape[1]
+    n = train_param_floats(nlayers, nf)
+    if loss is None:
+        loss = _empty((1 + B,), torch.float32, patches)
+    if want_grads and grads is None:
+        grads = _empty((n,), torch.float32, patches)
+    if workspace is None:
+        workspace = torch.empty(train_workspace_bytes(B, nlayers, nf), dtype=torch.uint8, device=patches.device)
+    pg = _need(grads, "grads", shape=(n,)) if want_grads else None
+    check(lib.sde_train_loss_grad(_need(patches, "patches", shape=(3, B, P, P)), B, _need(params, "params", shape=(n,)),
+                                  int(nlayers), int(nf), ctypes.c_float(margin), _need(loss, "loss", shape=(1 + B,)),
+                                  pg, _need(workspace, "workspace", dtype=torch.uint8), workspace.numel(), _stream()),
+          "sde_train_loss_grad")
+    return loss, (grads if want_grads else None)
+
+
+def train_export_activations(workspace, B: int, nlayers: int, layer: int, nf: int = 64, out=None):
+    """What the last train_loss_grad on `workspace` kept for the 1-based `layer`: f32 [3B,h,w,nf] post-ReLU
+    output (layer < nlayers) or the normalised features [3B,nf] (layer == nlayers)."""
+    s = 2 * (int(nlayers) - int(layer)) + 1
+    shape = (3 * B, nf) if layer == nlayers else (3 * B, s, s, nf)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=workspace.device)
+    check(lib.sde_train_export_activations(_need(workspace, "workspace", dtype=torch.uint8), int(B), int(nlayers),
+                                           int(nf), int(layer), _need(out, "out", shape=shape), _stream()),
+          "sde_train_export_activations")
+    return out
+
+
+def train_momentum(params, velocity, grads, lr: float, beta: float):
+    """In place: v = beta * v + g; p = p - lr * v, one fp32 rounding per operation (sde_train_momentum)."""
+    n = params.numel()
+    check(lib.sde_train_momentum(_need(params, "params", shape=(n,)), _need(velocity, "velocity", shape=(n,)),
+                                 _need(grads, "grads", shape=(n,)), n, ctypes.c_float(lr), ctypes.c_float(beta),
+                                 _stream()), "sde_train_momentum")
+    return params
