@@ -557,6 +557,64 @@ int sde_train_export_activations(const void *ws, int B, int nlayers, int nf, int
 int sde_train_momentum(float *params, float *velocity, const float *grads, int64_t n, float lr, float beta,
                        void *stream);
 
+/* ---------------------------------------------------------------------- */
+/* Training from resident stereo scenes (image_patches_prepare/*.py) and   */
+/* the bad-pixel rate (error_calculate.py).  Additive in ABI 4.            */
+/* ---------------------------------------------------------------------- */
+#define SDE_ZERO_IS_INVALID 1       /* sde_triplet_centres flag: a disparity of 0 marks an unknown pixel */
+#define SDE_SCENE_WORDS 8           /* int64 words per scene in the table of sde_train_sample_gather */
+#define SDE_SAMPLE_MAX_ROUNDS 32
+
+/*
+ * The valid patch centres of one scene.  h = nlayers, P = 2h + 1.  Pixel (y, x) with d = disp_l[y][x] is a
+ * centre iff (every comparison on the values widened to double)
+ *   d is finite, d >= 0 and, with SDE_ZERO_IS_INVALID, d != 0;
+ *   h <= y < H - h and h <= x < W - h;   d + h <= x;
+ *   with disp_r (may be NULL): r = disp_r[y][trunc(x - d)] is finite (with the flag, r != 0) and |r - d| <= 1.
+ * centres: int32, capacity H*W; on return its first *count entries hold y*W + x in ascending order.  The last
+ * H entries are used as scratch (per-row counts; no centre can land there: count <= (H-2)(W-2) <= H*W - H);
+ * nothing else is written.  count: one device int32.  Two launches, no atomics: the same maps give the same
+ * bytes.  SDE_ERR_ARG before any launch: H < P, W < P + 12, H*W >= 2^31, nlayers outside 1..5, unknown flag
+ * bits, a null disp_l / centres / count.
+ */
+int sde_triplet_centres(const float *disp_l, const float *disp_r, int H, int W, int nlayers, int flags,
+                        int32_t *centres, int32_t *count, void *stream);
+
+/*
+ * Draw B triplets from S resident scenes and gather their patches, in one launch.
+ * table: device int64 [S][SDE_SCENE_WORDS] = {img_l, img_r, disp_l, centres (device addresses), H, W, first,
+ * count}; img_* float32 [H][W] normalised images, disp_l the map sde_triplet_centres read, centres / count its
+ * result, first = the sum of count over the scenes before this one, N = the sum over all.  The library checks
+ * the scalars (S >= 1, 1 <= N < 2^31, B and nlayers as above, 1 <= max_rounds <= SDE_SAMPLE_MAX_ROUNDS, non-null
+ * table and patches) and TRUSTS THE TABLE: a table that does not describe live buffers of those sizes is the
+ * caller's error.
+ *
+ * Triplet i: Philox4x32-10 with key (seed lo, seed hi) and counter (i, step lo, step hi, tag) gives x0..x3;
+ * U = ((x0 << 21) | (x1 >> 11)) * 2^-53 in double.
+ *   centre    tag 0: g = (x0 * N) >> 32 (64-bit product); scene s has first_s <= g < first_s + count_s;
+ *             (y, x) from centres_s[g - first_s]; rc = (double)x - (double)disp_l_s[y][x]
+ *   positive  round r < max_rounds, tag 1 + r: pos = trunc(rc + (-0.501 + 1.002 * U)), accepted iff
+ *             h <= pos < W_s - h; no round accepted: pos = trunc(rc)
+ *   negative  round r, tag 33 + r: dev = 1.5 + 4.5 * U, neg = trunc(rc - dev) if x2 & 1 else trunc(rc + dev),
+ *             same test; no round accepted: neg = pos + 2 if that is accepted, else pos - 2
+ * every double operation rounded on its own.  patches: float32 [3][B][P][P] as sde_train_gather writes them
+ * from (y, x, pos, neg), a pixel outside the image reading 0; idx (optional): int32 [B][4] = (y, x, pos, neg);
+ * scene (optional): int32 [B].  The result depends on (seed, step, i, table) alone.
+ */
+int sde_train_sample_gather(const int64_t *table, int S, int64_t N, int B, int nlayers, uint64_t seed, uint64_t step,
+                            int max_rounds, float *patches, int32_t *idx, int32_t *scene, void *stream);
+
+/*
+ * error_calculate.py:72-81.  A pixel whose gt is +inf or 0 is skipped; any other is evaluated, and bad iff
+ * |(double)disp - (double)gt| > threshold (a NaN gt is evaluated and never bad).  counts: uint32 [2] =
+ * (evaluated, bad), ADDED to what the words hold (integer atomics, one per block and word: exact, order-free;
+ * the caller zeroes them and keeps the sum below 2^32).  area (optional): uint8 [H][W][3], every byte written:
+ * skipped 0,0,0; good 0,255,0; bad 0,0,255.  SDE_ERR_ARG: H or W < 1, H*W >= 2^31, a threshold that is negative
+ * or NaN, a null disp / gt / counts.
+ */
+int sde_bad_pixels(const float *disp, const float *gt, int H, int W, double threshold, uint32_t *counts,
+                   uint8_t *area, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,7 @@ import torch  # noqa: F401  (load torch's HIP runtime before libsde.so)
 from ._build import INCLUDE, LIB
 
 c_int, c_int64, c_float, c_double, c_void_p = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
-c_char_p = ctypes.c_char_p
+c_char_p, c_uint64 = ctypes.c_char_p, ctypes.c_uint64
 
 SDE_OK = 0
 SDE_ABI_VERSION = 4          # include/sde.h: the signatures below are this version's
@@ -34,6 +34,7 @@ SDE_CV_EXACT, SDE_CV_CERTIFIED = 0, 1
 SDE_SGM_ACCUMULATE = 1
 SDE_SGM_ZERO_DU_PENALTIES = 2
 SDE_LOCAL_MAX_RADIUS = 32
+SDE_ZERO_IS_INVALID, SDE_SCENE_WORDS, SDE_SAMPLE_MAX_ROUNDS = 1, 8, 32
 SDE_LOCAL_INVALID = 999999995904.0   # float32 nearest the reference's 999999999999 (bits 0x5368d4a5)
 
 # name -> (restype, argtypes); must cover every function declared in include/sde.h
@@ -105,6 +106,10 @@ SIGNATURES = {
                                     c_int64, c_void_p]),
     "sde_train_export_activations": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sde_train_momentum": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p]),
+    "sde_triplet_centres": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "sde_train_sample_gather": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_uint64, c_uint64, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    "sde_bad_pixels": (c_int, [c_void_p, c_void_p, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
 }
 
 

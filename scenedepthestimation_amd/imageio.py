@@ -54,3 +54,17 @@ def imwrite(path: str, img_u8) -> bool:
         os.makedirs(d, exist_ok=True)
     Image.fromarray(a, mode="L").save(path)
     return True
+
+
+def imwrite_bgr(path: str, img_u8) -> bool:
+    """An 8-bit [H][W][3] picture in OpenCV's channel order (blue, green, red), as cv2.imwrite takes it
+    (error_calculate.py:86)."""
+    from PIL import Image
+    a = np.asarray(img_u8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise TypeError("imwrite_bgr expects a uint8 [H][W][3] image")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    Image.fromarray(np.ascontiguousarray(a[:, :, ::-1]), mode="RGB").save(path)
+    return True

@@ -894,3 +894,61 @@ def train_momentum(params, velocity, grads, lr: float, beta: float):
                                  _need(grads, "grads", shape=(n,)), n, ctypes.c_float(lr), ctypes.c_float(beta),
                                  _stream()), "sde_train_momentum")
     return params
+
+
+# ----------------------------------------------------------------------------
+# training from resident scenes (image_patches_prepare/*.py) and the bad-pixel score (error_calculate.py)
+# ----------------------------------------------------------------------------
+def triplet_centres(disp_l, disp_r, nlayers: int, zero_is_invalid: bool = True, out=None, count=None):
+    """f32 [H,W] disparity maps (disp_r may be None) -> (centres int32 [H*W], count int32 [1]): the first
+    count[0] entries hold y*W + x of every valid patch centre in ascending order (sde_triplet_centres)."""
+    if disp_l.dim() != 2 or (disp_r is not None and tuple(disp_r.shape) != tuple(disp_l.shape)):
+        raise ValueError(f"disparity maps must be matching [H,W] tensors, got {tuple(disp_l.shape)}"
+                         + ("" if disp_r is None else f" / {tuple(disp_r.shape)}"))
+    H, W = disp_l.shape
+    if out is None:
+        out = _empty((H * W,), torch.int32, disp_l)
+    if count is None:
+        count = _empty((1,), torch.int32, disp_l)
+    pr = None if disp_r is None else _need(disp_r, "disp_r")
+    check(lib.sde_triplet_centres(_need(disp_l, "disp_l"), pr, H, W, int(nlayers),
+                                  _lib.SDE_ZERO_IS_INVALID if zero_is_invalid else 0,
+                                  _need(out, "centres", dtype=torch.int32, shape=(H * W,)),
+                                  _need(count, "count", dtype=torch.int32, shape=(1,)), _stream()),
+          "sde_triplet_centres")
+    return out, count
+
+
+def train_sample_gather(table, N: int, B: int, nlayers: int, seed: int, step: int, max_rounds: int = 32, out=None,
+                        idx=None, scene=None):
+    """Scene table int64 [S,8] (include/sde.h; its addresses are trusted) -> patches f32 [3,B,P,P] of B triplets
+    drawn on the device from (seed, step) (sde_train_sample_gather).  idx int32 [B,4] / scene int32 [B], when
+    given, receive (y, x_left, x_pos, x_neg) and the scene number of every triplet."""
+    if table.dim() != 2 or table.shape[1] != _lib.SDE_SCENE_WORDS:
+        raise ValueError(f"table must be [S,{_lib.SDE_SCENE_WORDS}], got {tuple(table.shape)}")
+    S, B, P = table.shape[0], int(B), 2 * int(nlayers) + 1
+    if out is None:
+        out = _empty((3, B, P, P), torch.float32, table)
+    pi = None if idx is None else _need(idx, "idx", dtype=torch.int32, shape=(B, 4))
+    ps = None if scene is None else _need(scene, "scene", dtype=torch.int32, shape=(B,))
+    mask = (1 << 64) - 1
+    check(lib.sde_train_sample_gather(_need(table, "table", dtype=torch.int64), S, int(N), B, int(nlayers),
+                                      int(seed) & mask, int(step) & mask, int(max_rounds),
+                                      _need(out, "patches", shape=(3, B, P, P)), pi, ps, _stream()),
+          "sde_train_sample_gather")
+    return out
+
+
+def bad_pixels(disp, gt, threshold: float = 1.0, counts=None, area=None):
+    """f32 [H,W] result and ground truth -> counts uint32-in-int32 [2] = (evaluated, bad), ADDED to what `counts`
+    holds (a fresh zeroed pair when None); area uint8 [H,W,3], when given, is the reference's error picture
+    (sde_bad_pixels)."""
+    if disp.dim() != 2 or tuple(gt.shape) != tuple(disp.shape):
+        raise ValueError(f"disp and gt must be matching [H,W] tensors, got {tuple(disp.shape)} / {tuple(gt.shape)}")
+    H, W = disp.shape
+    if counts is None:
+        counts = torch.zeros(2, dtype=torch.int32, device=disp.device)
+    pa = None if area is None else _need(area, "area", dtype=torch.uint8, shape=(H, W, 3))
+    check(lib.sde_bad_pixels(_need(disp, "disp"), _need(gt, "gt"), H, W, float(threshold),
+                             _need(counts, "counts", dtype=torch.int32, shape=(2,)), pa, _stream()), "sde_bad_pixels")
+    return counts

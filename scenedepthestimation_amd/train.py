@@ -1,12 +1,19 @@
 """Training of MC-CNN-fast on the GPU: the reference's train.py with its flags and defaults.
 
-    python -m scenedepthestimation_amd.train [--data pfm:<dir> | --data synthetic[:seed]] ...
+    python -m scenedepthestimation_amd.train [--data pfm:<dir> | synthetic[:seed] | scenes:<list.txt>] ...
 
 The reference's loop (train.py:137-174): per epoch, one pass over the training batches at learning rate
 lr / factor (factor = 10 once epoch + 1 > 10), a checkpoint every --save_freq epochs and a validation pass every
 --val_freq epochs.  Checkpoints are model_epoch{N}.npz with the reference's variable names plus the momentum
 slots, so --resume continues exactly; the validation loss is printed where the reference wrote TensorBoard
 scalars.
+
+--data scenes:<list.txt> trains from stereo scenes with ground truth instead of prepared patch files (the
+reference's image_patches_prepare/middlebury_*.py): one scene directory per line, as in its 2014.txt, each holding
+the four --scene-files.  The scenes stay on the device (training.SceneSet) and every batch is drawn there: epoch e,
+batch k is step e * batches_per_epoch + k of one seeded stream, so --resume with --start_epoch continues it.  The
+last --val-scenes scenes are held out: their batches (another seed, from step 0 every epoch) give the validation
+loss, and the current weights are matched on them and scored with evaluation.bad_pixel_rate.
 """
 from __future__ import annotations
 
@@ -14,6 +21,8 @@ import argparse
 import os
 import sys
 from datetime import datetime
+
+import numpy as np
 
 # the reference's patch numbering (train.py:48-61)
 TRAIN_HEAD, TRAIN_TAIL = 0, 1898240
@@ -38,9 +47,20 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--save_freq", type=int, default=1, help="write a checkpoint every this many epochs")
     p.add_argument("--val_freq", type=int, default=1, help="run the validation pass every this many epochs")
     p.add_argument("--data", type=str, default="pfm:./training_data_set",
-                   help="pfm:<dir> with left/ right_pos/ right_neg/{n}.pfm, or synthetic[:seed]")
+                   help="pfm:<dir> with left/ right_pos/ right_neg/{n}.pfm, synthetic[:seed], or scenes:<list.txt> "
+                        "with one scene directory per line")
     p.add_argument("--steps-per-epoch", type=int, default=None,
-                   help="batches per epoch (default: the whole pfm set; 100 for synthetic data)")
+                   help="batches per epoch (default: the whole pfm set; 100 for synthetic data; centres // batch "
+                        "size for scenes)")
+    p.add_argument("--scene-files", type=str, default="im0.png,im1.png,disp0.pfm,disp1.pfm",
+                   help="scenes: left image, right image, left disparity, right disparity inside each directory "
+                        "(leave the fourth empty to train without the left-right check)")
+    p.add_argument("--half", action="store_true",
+                   help="scenes: halve images and maps by 2x2 means and divide the disparities by 2 "
+                        "(middlebury_2014.py:119-124)")
+    p.add_argument("--val-scenes", type=int, default=0, help="scenes: hold out the last K scenes for validation")
+    p.add_argument("--val-ndisp", type=int, default=128, help="scenes: disparity range of the validation match")
+    p.add_argument("--seed", type=int, default=0, help="scenes: seed of the triplet stream")
     p.add_argument("--checkpoint-dir", type=str, default="./check_points_mr30")
     return p
 
@@ -61,15 +81,107 @@ class _SyntheticSource:
         self.seed = self.seed0
 
 
+def read_scene_list(path: str):
+    """One scene directory per line (blank lines skipped), as the reference's 2014.txt."""
+    with open(path) as fh:
+        return [ln.strip() for ln in fh if ln.strip()]
+
+
+def load_scene(directory: str, files, half: bool):
+    """-> (left u8, right u8, left disparity f32, right disparity f32 or None), halved if asked."""
+    from .evaluation import halve, halve_u8
+    from .imageio import imread_gray
+    from .pfm import load_pfm
+    if len(files) != 4:
+        raise SystemExit("--scene-files takes four comma-separated names (the fourth may be empty)")
+    imgs = []
+    for name in files[:2]:
+        img = imread_gray(os.path.join(directory, name))
+        if img is None:
+            raise SystemExit(f"cannot read {os.path.join(directory, name)}")
+        imgs.append(halve_u8(img) if half else img)
+    maps = []
+    for name in files[2:]:
+        if not name:
+            maps.append(None)
+            continue
+        m = np.ascontiguousarray(load_pfm(os.path.join(directory, name))[0][:, :, 0], dtype=np.float32)
+        maps.append(halve(m) / np.float32(2) if half else m)
+    return imgs[0], imgs[1], maps[0], maps[1]
+
+
+class _SceneSource:
+    """Batches of a training.SceneSet: handles the trainer resolves on the device.  The training stream runs on
+    across epochs (reset_pointer leaves it alone); the validation stream restarts at step 0."""
+
+    def __init__(self, scene_set, batch: int, steps: int, first_step: int, restart: bool):
+        self.set, self.batch, self.dataset_size, self.restart = scene_set, batch, steps, restart
+        self.step = first_step
+
+    def next_batch(self):
+        self.step += 1
+        return self.set.batch(self.step - 1, self.batch)
+
+    def reset_pointer(self):
+        if self.restart:
+            self.step = 0
+
+
+def _scene_sources(args, path: str):
+    from .training import SceneSet
+    dirs = read_scene_list(path)
+    files = args.scene_files.split(",")
+    k = args.val_scenes
+    if not 0 <= k < len(dirs):
+        raise SystemExit(f"--val-scenes {k}: the list holds {len(dirs)} scenes and one must be left to train on")
+    scenes = [load_scene(d, files, args.half) for d in dirs]
+    L = args.patch_size // 2
+    train = SceneSet(scenes[:len(dirs) - k], nlayers=L, seed=2 * args.seed, device="cuda:0")
+    for i in train.skipped:
+        print(f"scene {dirs[i]} has no valid patch centre: skipped")
+    steps = args.steps_per_epoch or max(1, train.N // args.batch_size)
+    out = _SceneSource(train, args.batch_size, steps, args.start_epoch * steps, restart=False)
+    if k == 0:
+        return out, None, []
+    val = SceneSet(scenes[len(dirs) - k:], nlayers=L, seed=2 * args.seed + 1, device="cuda:0")
+    vsteps = max(1, min(val.N // args.batch_size, max(1, steps // 10)))
+    return out, _SceneSource(val, args.batch_size, vsteps, 0, restart=True), scenes[len(dirs) - k:]
+
+
+def validation_bad_pixels(weights, scenes, nlayers: int, ndisp: int, matchers: dict, threshold: float = 1.0):
+    """Match every held-out scene with `weights` (one StereoMatcher per distinct size, kept in `matchers`) and score
+    it against its left ground truth -> (mean rate over the image, mean rate over the evaluated pixels)."""
+    import torch
+
+    from . import mc_cnn, ops
+    from .evaluation import bad_pixel_rate
+    from .pipeline import StereoMatcher
+    hw, hb = mc_cnn.layer_lists(weights, nlayers)
+    packed = torch.from_numpy(ops.pack_tower_weights(hw, hb))
+    rates = []
+    for left, right, disp_l, _ in scenes:
+        H, W = left.shape
+        m = matchers.get((H, W))
+        if m is None:
+            m = matchers[H, W] = StereoMatcher(H, W, min(ndisp, W), weights=weights, nlayers=nlayers, device="cuda:0")
+        m.packed.copy_(packed)
+        m.load_images(left, right)
+        r = bad_pixel_rate(m.match(), torch.from_numpy(disp_l).to(m.device), threshold)
+        rates.append((r["rate_over_image"], r["rate_over_evaluated"]))
+    return tuple(float(np.mean(c)) for c in zip(*rates))
+
+
 def _sources(args):
     kind, _, rest = args.data.partition(":")
+    if kind == "scenes":
+        return _scene_sources(args, rest)
     if kind == "synthetic":
         seed = int(rest) if rest else 0
         steps = args.steps_per_epoch or 100
         return (_SyntheticSource(2 * seed * 1000003, args.batch_size, args.patch_size, steps),
-                _SyntheticSource((2 * seed + 1) * 1000003, args.batch_size, args.patch_size, max(1, steps // 10)))
+                _SyntheticSource((2 * seed + 1) * 1000003, args.batch_size, args.patch_size, max(1, steps // 10)), [])
     if kind != "pfm":
-        raise SystemExit(f"--data {args.data}: expected pfm:<dir> or synthetic[:seed]")
+        raise SystemExit(f"--data {args.data}: expected pfm:<dir>, synthetic[:seed] or scenes:<list.txt>")
     from .training import PatchFileDataset
     root = rest or "./training_data_set"
     paths = [os.path.join(root, sub, "{}.pfm") for sub in ("left", "right_pos", "right_neg")]
@@ -78,7 +190,7 @@ def _sources(args):
     val = PatchFileDataset(*paths, VAL_HEAD, VAL_TAIL, patch_size=size, batch_size=args.batch_size, shuffle=False)
     if args.steps_per_epoch:
         train.dataset_size = min(train.dataset_size, args.steps_per_epoch)
-    return train, val
+    return train, val, []
 
 
 def main(argv=None) -> int:
@@ -98,8 +210,10 @@ def main(argv=None) -> int:
                       beta=args.beta, device="cuda:0")
     if args.resume is not None:
         trainer.load(args.resume)
-    train_set, val_set = _sources(args)
-    print(f"batches per epoch: {train_set.dataset_size} training, {val_set.dataset_size} validation")
+    train_set, val_set, val_scenes = _sources(args)
+    matchers = {}
+    print(f"batches per epoch: {train_set.dataset_size} training, "
+          f"{val_set.dataset_size if val_set is not None else 0} validation")
     for epoch in range(args.start_epoch, args.end_epoch):
         print(f"{datetime.now()} epoch {epoch + 1}")
         fac = 10 if epoch + 1 > 10 else 1
@@ -112,11 +226,16 @@ def main(argv=None) -> int:
             path = os.path.join(args.checkpoint_dir, f"model_epoch{epoch + 1}.npz")
             trainer.save(path)
             print(f"{datetime.now()} wrote {path}")
-        if (epoch + 1) % args.val_freq == 0:
+        if (epoch + 1) % args.val_freq == 0 and val_set is not None:
             val_ls = sum(trainer.loss(val_set.next_batch()) for _ in range(val_set.dataset_size))
             print(f"validation loss: {val_ls / max(1, val_set.dataset_size)}")
+            if val_scenes:
+                over_image, over_evaluated = validation_bad_pixels(trainer.weights(), val_scenes, trainer.nlayers,
+                                                                   args.val_ndisp, matchers)
+                print(f"validation bad-pixel rate: {over_image} of the image, {over_evaluated} of the evaluated pixels")
         train_set.reset_pointer()
-        val_set.reset_pointer()
+        if val_set is not None:
+            val_set.reset_pointer()
     return 0
 
 

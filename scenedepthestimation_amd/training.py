@@ -5,6 +5,9 @@
                      enqueued on the current stream with no read-back and no allocation
   TripletSampler     seeded host-side choice of (y, x_left, x_pos, x_neg) patch centres from a disparity map, by
                      the rule of the reference's patch preparation (image_patches_prepare/middlebury_2003.py:81-110)
+  SceneSet           stereo scenes with ground truth resident on the device; its batches are drawn (counter-based
+                     RNG) and gathered there in one launch, by the same rule (sde_triplet_centres,
+                     sde_train_sample_gather): no host draw, no copy, no read-back per step
   PatchFileDataset   the reference's ImagePatchesGenerator over per-patch .pfm files (data_generator.py)
 
 torch is plumbing here (device memory, streams): no torch.nn, no autograd.
@@ -128,6 +131,78 @@ def synthetic_triplets(seed: int, batch: int, patch: int = 11, H: int = 64, W: i
     return normalise(left), normalise(right), idx
 
 
+class SceneBatch:
+    """What SceneSet.batch returns: batch `step` of `B` triplets, drawn when a Trainer resolves it."""
+    __slots__ = ("scenes", "step", "B")
+
+    def __init__(self, scenes, step: int, B: int):
+        self.scenes, self.step, self.B = scenes, int(step), int(B)
+
+
+class SceneSet:
+    """Stereo scenes with ground truth, resident on the device, as a source of training batches.
+
+    scenes: [(img_l_u8, img_r_u8, disp_l, disp_r or None)], images [H][W] (uint8 or anything `normalise` takes),
+    disparity maps [H][W] floats.  Every image is normalised as the reference prepares it and uploaded with its
+    left map; ops.triplet_centres compacts the scene's valid centres (TripletSampler's rule) on the device, with
+    one count read back per scene, here and never later.  A scene without a centre is left out (its number is in
+    `.skipped`); a set without any raises.  `.batch(step, B)` is a handle that Trainer.step / Trainer.loss resolve
+    with ops.train_sample_gather into the trainer's own patch buffer: triplet i of batch `step` depends on
+    (seed, step, i) and the scenes alone, whatever was drawn before.
+    """
+
+    def __init__(self, scenes, nlayers: int = 5, seed: int = 0, zero_is_invalid: bool = True, max_rounds: int = 32,
+                 device=None):
+        import torch
+
+        from . import ops
+        self.nlayers, self.seed, self.max_rounds = int(nlayers), int(seed), int(max_rounds)
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise ValueError(f"SceneSet needs a GPU device, got {self.device}")
+
+        def up(a, dtype=np.float32):
+            return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.device)
+
+        self.skipped, self.shapes, self.counts, self._keep, rows = [], [], [], [], []
+        first = 0
+        with torch.cuda.device(self.device):
+            for k, (img_l, img_r, disp_l, disp_r) in enumerate(scenes):
+                il, ir, dl = up(normalise(img_l)), up(normalise(img_r)), up(disp_l)
+                if il.dim() != 2 or il.shape != ir.shape or il.shape != dl.shape:
+                    raise ValueError(f"scene {k}: images and disparity map must share one [H][W] shape, got "
+                                     f"{tuple(il.shape)} / {tuple(ir.shape)} / {tuple(dl.shape)}")
+                dr = None if disp_r is None else up(disp_r)
+                centres, count = ops.triplet_centres(dl, dr, self.nlayers, zero_is_invalid)
+                n = int(count.item())
+                if n == 0:
+                    self.skipped.append(k)
+                    continue
+                centres = centres[:n].clone()
+                H, W = il.shape
+                rows.append([il.data_ptr(), ir.data_ptr(), dl.data_ptr(), centres.data_ptr(), H, W, first, n])
+                self._keep.append((il, ir, dl, centres))
+                self.shapes.append((H, W))
+                self.counts.append(n)
+                first += n
+            if not rows:
+                raise ValueError("no scene has a valid patch centre")
+            self.N = first
+            self.table = torch.tensor(rows, dtype=torch.int64).to(self.device)
+
+    def __len__(self) -> int:
+        return len(self.counts)
+
+    def batch(self, step: int, B: int) -> SceneBatch:
+        return SceneBatch(self, step, B)
+
+    def gather(self, step: int, B: int, out=None, idx=None, scene=None):
+        """Batch `step` into `out` (f32 [3][B][P][P]); idx / scene as ops.train_sample_gather takes them."""
+        from . import ops
+        return ops.train_sample_gather(self.table, self.N, B, self.nlayers, self.seed, step, self.max_rounds,
+                                       out=out, idx=idx, scene=scene)
+
+
 class PatchFileDataset:
     """The reference's ImagePatchesGenerator: per-patch files path.format(number), numbers head .. tail - 1, read
     in list order (a permutation drawn from NumPy's global state when shuffle, as the reference does; seed it with
@@ -214,8 +289,13 @@ class Trainer:
 
     def _patches(self, data):
         """[3,B,P,P] patches from: such a tensor / array; three [B,P,P(,1)] arrays (PatchFileDataset.next_batch);
-        or (img_l, img_r, idx), gathered on the device."""
+        (img_l, img_r, idx), gathered on the device; or a SceneBatch, drawn and gathered on the device."""
         t = self._torch
+        if isinstance(data, SceneBatch):
+            if data.scenes.nlayers != self.nlayers or data.scenes.device != self.device:
+                raise ValueError(f"the scene set is for {data.scenes.nlayers} layers on {data.scenes.device}, the "
+                                 f"trainer for {self.nlayers} on {self.device}")
+            return data.scenes.gather(data.step, data.B, out=self._buffers(data.B)[2])
         if isinstance(data, (tuple, list)) and len(data) == 3:
             third = data[2]
             if third.ndim == 2 and third.shape[1] == 4 and not (third.dtype.is_floating_point if isinstance(
