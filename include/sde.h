@@ -412,7 +412,17 @@ int sde_cbca_lr(float *cv_l, float *cv_r, float *tmp, const uint32_t *arms_l, co
  * kernels compute it (the tests check them against the IEEE quotient). */
 int sde_cbca_reciprocals(double *out, int n, void *stream);
 
-/* is_error_match_kernel (process_functional.py:977-1000): lrc_l/lrc_r u8 [H][W], caller-zeroed. */
+/*
+ * is_error_match_kernel (process_functional.py:977-1000): lrc_l / lrc_r u8 [H][W], caller-zeroed.  In float64,
+ * with col = the reference's uint8 cast of c (truncation toward zero, then the low byte of the two's-complement
+ * integer; 0 for |c| >= 2^63, whose low byte is 0):
+ *   left  pixel, d = disp_l[y][x], c = x - d: if 0 <= c < +inf and col < W, lrc_l = |d - disp_r[y][col]| > 1
+ *   right pixel, d = disp_r[y][x], c = x + d: if -inf < c < W  and col < W, lrc_r = |d - disp_l[y][col]| > 1
+ * Every other pixel is skipped: its byte stays as the caller set it.  That covers a NaN or infinite c, and for
+ * W < 256 a cast column past the row (a left -1 at x = W - 1 gives column W, a right -1 at x = 0 column 255; -1
+ * is what sde_wta's SDE_WTA_INIT_INF writes for "no winner").  Never reads outside the row, and the result is
+ * defined for every float input.
+ */
 int sde_lr_check(const float *disp_l, const float *disp_r, int H, int W, uint8_t *lrc_l, uint8_t *lrc_r,
                  void *stream);
 

@@ -5,8 +5,9 @@
  *
  * Build + run: `make -C oracle asan` (tests/test_oracle.py::test_oracle_asan).  Shapes
  * cover the edges the kernels' tests use: 1-pixel and 2-pixel lines, D > W, D not a
- * multiple of 4, C not a multiple of 8, L1 at its maximum, fully flagged LRC maps, and
- * non-finite costs in SGM.
+ * multiple of 4, C not a multiple of 8, L1 at its maximum, fully flagged LRC maps,
+ * non-finite costs in SGM, and disparity maps narrower than 256 columns with -1, NaN and
+ * +-inf entries, whose uint8 column cast points outside the row (or has no integer value).
  */
 #include "sde_oracle.c"
 
@@ -45,7 +46,7 @@ static void run_cv(int H, int W, int C, int D)
     free(fl); free(fr); free(dhw); free(l); free(r); free(disp); free(mn); free(am);
 }
 
-static void run_sgm_post(int H, int W, int D, int nonfinite)
+static void run_sgm_post(int H, int W, int D, int nonfinite, int lr_edges)
 {
     uint8_t *img = (uint8_t *)malloc((size_t)H * W), *a = (uint8_t *)calloc((size_t)H * W, 1),
             *b = (uint8_t *)calloc((size_t)H * W, 1);
@@ -58,6 +59,19 @@ static void run_sgm_post(int H, int W, int D, int nonfinite)
     if (H >= 2 && W >= 2) sdeo_sgm_8path(cv, pen, H, W, D, S);
     sdeo_wta_sgm_hwd(S, H, W, D, dl);
     for (size_t i = 0; i < (size_t)H * W; i++) dr[i] = (float)(int)((frand() + 1.0f) * 4.0f);
+    if (lr_edges) {
+        /* -1 is sde_wta's "no winner": left x = W-1 -> column W, right x = 0 -> column 255 */
+        const float edge[] = {-1.0f, NAN, INFINITY, -INFINITY, -0.5f, 1e9f, -1e9f, 3e38f, -3e38f};
+        const size_t n = (size_t)H * W, ne = sizeof(edge) / sizeof(edge[0]);
+        for (size_t k = 0; k < ne && k + 1 < n; k++) {
+            dl[1 + k] = edge[k];
+            dr[n - 2 - k] = edge[k];
+            dl[n - 2 - k - ne] = edge[ne - 1 - k];
+            dr[1 + k + ne] = edge[ne - 1 - k];
+        }
+        dl[n - 1] = dl[W - 1] = -1.0f;
+        dr[0] = dr[n - W] = -1.0f;
+    }
     sdeo_lr_check(dl, dr, H, W, a, b);
     sdeo_lrc_fill(dl, a, H, W, out);
     memset(a, 1, (size_t)H * W);                 /* fully flagged: every walk runs off the image */
@@ -104,11 +118,14 @@ int main(void)
         run_cv(4, 9, 20, 5);
         run_cv(2, 5, 136, 9);
         run_cv(2, 3, 1, 4);
-        run_sgm_post(2, 2, 4, 0);
-        run_sgm_post(6, 9, 12, 1);
-        run_sgm_post(9, 3, 7, 0);
-        run_sgm_post(3, 9, 130, 1);
-        run_sgm_post(1, 6, 8, 0);
+        run_sgm_post(2, 2, 4, 0, 0);
+        run_sgm_post(6, 9, 12, 1, 0);
+        run_sgm_post(9, 3, 7, 0, 0);
+        run_sgm_post(3, 9, 130, 1, 0);
+        run_sgm_post(1, 6, 8, 0, 0);
+        run_sgm_post(6, 40, 4, 0, 1);
+        run_sgm_post(3, 255, 4, 0, 1);
+        run_sgm_post(2, 256, 4, 0, 1);
         run_tower(3, 4, 1);
         run_tower(5, 6, 3);
         run_cbca(9, 13, 6, 32);

@@ -105,23 +105,24 @@ def cost_volume_hwd(featuresl, featuresr, ndisp, invalid=1.0, right=True):
     return (outl, outr) if right else outl
 
 
-def WTA1(cv):
-    """WTA1 (process_functional.py:96-113) on [D,H,W]."""
+def WTA1(cv, strict=True):
+    """WTA1 (process_functional.py:96-113) on [D,H,W].  strict: a pixel with no cost below +inf is an error, as
+    the reference asserts; otherwise it reads -1."""
     cv = _c32(cv)
     D, H, W = cv.shape
     out = np.empty((H, W), np.float32)
     bad = lib().sdeo_wta1_dhw(_p(cv), D, H, W, _p(out))
-    assert bad == 0
+    assert bad == 0 or not strict
     return out
 
 
-def WTA(cv):
-    """WTA (process_functional.py:76-93) on [H,W,D]."""
+def WTA(cv, strict=True):
+    """WTA (process_functional.py:76-93) on [H,W,D]; strict as for WTA1."""
     cv = _c32(cv)
     H, W, D = cv.shape
     out = np.empty((H, W), np.float32)
     bad = lib().sdeo_wta_hwd(_p(cv), H, W, D, _p(out))
-    assert bad == 0
+    assert bad == 0 or not strict
     return out
 
 
@@ -193,12 +194,14 @@ def sgm_8path(cv_hwd, pen, S=None):
     return S
 
 
-def lr_check(dl, dr):
-    """is_error_match_kernel (process_functional.py:977-1000) -> (lrc_l, lrc_r) u8, zero-initialised."""
+def lr_check(dl, dr, init_l=None, init_r=None):
+    """is_error_match_kernel (process_functional.py:977-1000) -> (lrc_l, lrc_r) u8, starting from copies of
+    init_l / init_r (zeros by default): a pixel the check skips keeps that byte."""
     dl, dr = _c32(dl), _c32(dr)
     H, W = dl.shape
-    a = np.zeros((H, W), np.uint8)
-    b = np.zeros((H, W), np.uint8)
+    a = np.zeros((H, W), np.uint8) if init_l is None else np.array(init_l, dtype=np.uint8, order="C", copy=True)
+    b = np.zeros((H, W), np.uint8) if init_r is None else np.array(init_r, dtype=np.uint8, order="C", copy=True)
+    assert a.shape == (H, W) and b.shape == (H, W)
     lib().sdeo_lr_check(_p(dl), _p(dr), H, W, _p(a, _u8p), _p(b, _u8p))
     return a, b
 

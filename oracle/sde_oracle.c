@@ -425,8 +425,16 @@ EXPORT void sdeo_sgm_8path(const float *cv, const float *pen, int H, int W, int 
 /* uint8() index casts are restated as truncation toward zero then mod 256  */
 /* (PARITY UNPINNED: Numba's float->uint8 out-of-range behaviour).           */
 /* ------------------------------------------------------------------------ */
-static inline int u8cast(double v) { long long t = (long long)v; return (int)(t & 255); }
+/* |v| >= 2^63 does not fit the cast; such a double is a multiple of 2^11, so its low byte is 0. */
+static inline int u8cast(double v)
+{
+    if (v >= 0x1p63 || v <= -0x1p63) return 0;
+    long long t = (long long)v;
+    return (int)(t & 255);
+}
 
+/* A pixel whose column value is not finite, or whose cast column is >= W, is skipped: its flag byte stays as
+ * the caller set it and nothing outside the row is read (the rule of sde_lr_check, include/sde.h). */
 EXPORT void sdeo_lr_check(const float *dl, const float *dr, int H, int W, uint8_t *lrcl, uint8_t *lrcr)
 {
 #pragma omp parallel for num_threads(g_threads) schedule(static)
@@ -434,17 +442,23 @@ EXPORT void sdeo_lr_check(const float *dl, const float *dr, int H, int W, uint8_
         for (int x = 0; x < W; x++) {
             double ld = dl[(size_t)y * W + x];
             double rd = (double)x - ld;
-            if (rd >= 0) {
-                double r2 = dr[(size_t)y * W + u8cast(rd)];
-                double mn = ld - r2;
-                lrcl[(size_t)y * W + x] = (mn > 1 || mn < -1) ? 1 : 0;
+            if (rd >= 0 && rd < INFINITY) {
+                int col = u8cast(rd);
+                if (col < W) {
+                    double r2 = dr[(size_t)y * W + col];
+                    double mn = ld - r2;
+                    lrcl[(size_t)y * W + x] = (mn > 1 || mn < -1) ? 1 : 0;
+                }
             }
             double rd2 = dr[(size_t)y * W + x];
             double ld2 = (double)x + rd2;
-            if (ld2 < W) {
-                double l2 = dl[(size_t)y * W + u8cast(ld2)];
-                double mn = rd2 - l2;
-                lrcr[(size_t)y * W + x] = (mn > 1 || mn < -1) ? 1 : 0;
+            if (ld2 < W && ld2 > -INFINITY) {
+                int col = u8cast(ld2);
+                if (col < W) {
+                    double l2 = dl[(size_t)y * W + col];
+                    double mn = rd2 - l2;
+                    lrcr[(size_t)y * W + x] = (mn > 1 || mn < -1) ? 1 : 0;
+                }
             }
         }
 }

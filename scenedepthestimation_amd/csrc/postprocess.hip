@@ -7,8 +7,16 @@
 
 namespace sde {
 
-__device__ __forceinline__ int u8cast(double v) { return (int)((long long)v & 255); }
+// The reference's uint8(v) of a finite v: truncation toward zero, then the low byte of the two's-complement
+// integer.  |v| >= 2^63 does not fit the cast; such a double is a multiple of 2^11, so its low byte is 0.
+__device__ __forceinline__ int u8cast(double v)
+{
+    if (v >= 0x1p63 || v <= -0x1p63) return 0;
+    return (int)((long long)v & 255);
+}
 
+// A pixel whose column value (x - d left, x + d right) is not finite, or whose cast column is >= W, is skipped:
+// its flag byte stays as the caller set it, and nothing outside the row is read.
 __global__ __launch_bounds__(256) void lr_check_kernel(const float *__restrict__ dl, const float *__restrict__ dr,
                                                        int H, int W, uint8_t *__restrict__ lrcl,
                                                        uint8_t *__restrict__ lrcr)
@@ -18,15 +26,21 @@ __global__ __launch_bounds__(256) void lr_check_kernel(const float *__restrict__
     const int y = (int)(p / W), x = (int)(p % W);
     const double ld = dl[p];
     const double rd = (double)x - ld;
-    if (rd >= 0) {
-        const double mn = ld - (double)dr[(size_t)y * W + u8cast(rd)];
-        lrcl[p] = (mn > 1 || mn < -1) ? 1 : 0;
+    if (rd >= 0 && rd < (double)__builtin_inf()) {
+        const int col = u8cast(rd);
+        if (col < W) {
+            const double mn = ld - (double)dr[(size_t)y * W + col];
+            lrcl[p] = (mn > 1 || mn < -1) ? 1 : 0;
+        }
     }
     const double rd2 = dr[p];
     const double ld2 = (double)x + rd2;
-    if (ld2 < W) {
-        const double mn = rd2 - (double)dl[(size_t)y * W + u8cast(ld2)];
-        lrcr[p] = (mn > 1 || mn < -1) ? 1 : 0;
+    if (ld2 < W && ld2 > -(double)__builtin_inf()) {
+        const int col = u8cast(ld2);
+        if (col < W) {
+            const double mn = rd2 - (double)dl[(size_t)y * W + col];
+            lrcr[p] = (mn > 1 || mn < -1) ? 1 : 0;
+        }
     }
 }
 

@@ -107,6 +107,9 @@ def test_tower_packing_matches_layout():
 
 
 def test_argument_validation_without_gpu():
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("passes made-up addresses, which is only safe while no device can be launched on")
     lib = _lib.lib
     ERR = -1
     assert lib.sde_cost_volume(None, None, 4, 4, 64, 4, 0, 1, ctypes.c_float(0.0), None, None, None) == ERR
