@@ -178,6 +178,11 @@ int sde_set_persistent_grid(int cus);
 /* With SDE_TOWER_F16X3 only: run the 64 -> 64 layers on the v_mfma_f32_32x32x16_f16 direct kernel instead of
  * the default v_mfma_f32_16x16x32_f16 one (same arithmetic contract). */
 #define SDE_TOWER_MFMA32 32
+/* With SDE_TOWER_F16X3, not with MFMA32: keep every layer of the v_mfma_f32_16x16x32_f16 path on the 16 x 32-tile
+ * kernel.  Without it, layers 3..L with fp32 activations in and out (no IN_SPLIT / OUT_SPLIT, no split feature planes)
+ * run the 16 x 16-tile kernel whose stager waves store the outputs; the bits are the same either way, and the
+ * flag changes nothing for the layers only the 16 x 32 kernel serves. */
+#define SDE_TOWER_TILE32 256
 #define SDE_TOWER_IN_CBLOCK 2
 #define SDE_TOWER_OUT_CBLOCK 4
 /* F16X3 split activations (sde_tower_layer_scaled / sde_tower_layer_batch; what sde_tower_forward uses

@@ -139,9 +139,15 @@ static void launch_layer(TowerLaunch L, const float *packed, int nlayers, int la
     const bool wino_fits = (int64_t)L.Hin * L.Win * 256 < ((int64_t)1 << 32) &&
                            (int64_t)L.hout * L.wout * 256 < ((int64_t)1 << 32);
     const bool wino = L.f16 && layer >= 3 && !L.ohi && !L.onrm && (flags & SDE_TOWER_WINOGRAD) && wino_fits;
-    L.grid = xp_batch(L.bt, wino ? WN_TX : XP_TX, wino ? WN_TY : XP_TY, L.hout, L.wout, L.nimg);
+    // the 16x16x32 kernels: layers 3..L run 16 x 16 tiles with the stores on the stager waves (tower_h16s.h) where
+    // the activations are fp32 and no split feature planes are asked for, unless SDE_TOWER_TILE32 keeps the 16 x 32
+    // kernel; layer 2 always runs the 16 x 32 kernel (its stagers compute conv1: +9 % with the stores on top)
+    const bool h16k = !wino && h16 && (layer >= 3 || !L.last);
+    const bool h16s = h16k && !L.first && !(flags & SDE_TOWER_TILE32) && !L.in_sp && !L.out_sp && !L.ohi && !L.onrm;
+    L.grid = xp_batch(L.bt, wino ? WN_TX : h16s ? 16 : XP_TX, wino ? WN_TY : XP_TY, L.hout, L.wout, L.nimg);
     if (wino) launch_wino(L);
-    else if (h16 && (layer >= 3 || !L.last)) launch_h16(L);
+    else if (h16s) launch_h16s(L);
+    else if (h16k) launch_h16(L);
     else if (x6) launch_x6p(L);
     else launch_fp32(L);
 }
@@ -181,6 +187,10 @@ static bool tower_flags_ok(int flags, bool layer_api)
         if ((flags & SDE_TOWER_IN_SPLIT && flags & SDE_TOWER_IN_CBLOCK) ||
             (flags & SDE_TOWER_OUT_SPLIT && flags & SDE_TOWER_OUT_CBLOCK)) return false;
         flags &= ~(SDE_TOWER_IN_SPLIT | SDE_TOWER_OUT_SPLIT);
+    }
+    if (flags & SDE_TOWER_TILE32) {   // F16X3 on the 16x16x32 kernels: their tile (a no-op where only the 16 x 32 kernel exists)
+        if (!(flags & SDE_TOWER_F16X3) || (flags & SDE_TOWER_MFMA32)) return false;
+        flags &= ~SDE_TOWER_TILE32;
     }
     if (flags & (SDE_TOWER_WINOGRAD | SDE_TOWER_MFMA32)) {   // F16X3 only: the 64 -> 64 layers' kernel choice
         if (!(flags & SDE_TOWER_F16X3) || (flags & SDE_TOWER_WINOGRAD && flags & SDE_TOWER_MFMA32)) return false;

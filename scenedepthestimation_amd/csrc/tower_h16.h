@@ -57,16 +57,36 @@ static_assert(H16_SMEM_FIRST <= 163840, "LDS (layer 2)");
 // (profiles/r05/tower_act_aux_nt.txt); 2 (nt) did not help.
 constexpr int H16_ACT_AUX = 1;
 
+// Tile geometry of a kernel of this family, for the code the families share (the stager loops, the B fragments):
+// H16T32 is conv64_h16_kernel's 16 x 32 tile (the XP_ constants, as in conv64_x6p_kernel); tower_h16s.h has the
+// 16 x 16 tile.  HANDOFF: the stager waves also drain the tile outputs the MFMA waves park in LDS (tower_h16s.h).
+struct H16T32 {
+    static constexpr int TY = XP_TY, TX = XP_TX, IY = XP_IY, IX = XP_IX, NPIX = XP_NPIX, UNITS = XP_UNITS, UPT = XP_UPT;
+    static constexpr int PLANE = H16_PLANE, STAGE = H16_STAGE;
+    static constexpr bool HANDOFF = false;
+};
+
+// tile t of a launch -> image, output origin (xp_tile for T's tile)
+template <class T>
+__device__ __forceinline__ void h16_tile(const XpBatch &bt, int t, int &img, int &ty0, int &tx0)
+{
+    img = t / bt.tiles_img;
+    const int tl = t - img * bt.tiles_img;
+    ty0 = (tl / bt.tiles_x) * T::TY;
+    tx0 = (tl % bt.tiles_x) * T::TX;
+}
+
 // Split 4 channels, scaled by s, into the stage's (part, quarter) planes at dst (the unit's byte offset
 // in the stage, see h16_stager_loop): hi = f16(x s) by packed converts, lo = f16(x s - hi) by v_fma_mix from the
 // packed hi half (xp_split16s; x s - hi is exact in fp32, so the same bits as the per-value split).  8 instead of
 // 20 VALU per unit: the stagers' work per launch 222 -> 136 kcycles (profiles/r06/tower_phase_*.txt).
+template <class T = H16T32>
 __device__ __forceinline__ void h16_put(char *dst, float4 v, float s)
 {
     u32x2 hw, lw;
     xp_split16s(make_float4(v.x * s, v.y * s, v.z * s, v.w * s), hw, lw);
     *reinterpret_cast<uint2 *>(dst) = __builtin_bit_cast(uint2, hw);
-    *reinterpret_cast<uint2 *>(dst + 4 * H16_PLANE) = __builtin_bit_cast(uint2, lw);
+    *reinterpret_cast<uint2 *>(dst + 4 * T::PLANE) = __builtin_bit_cast(uint2, lw);
 }
 
 // Stage unit (pixel << 2 | 4-channel chunk) of stager thread st at iteration i: a wave's lanes take 16
@@ -82,7 +102,7 @@ __device__ __forceinline__ int h16_unit(int st, int i)
     const int px = (i * (XP_STAGERS / 64) + (st >> 6)) * 16 + ((l >> 4) & 1) * 8 + ((l >> 1) & 7);
     return px * 4 + ((l >> 5) << 1 | (l & 1));
 }
-static_assert(XP_UPT * XP_STAGERS / 4 >= XP_NPIX, "the stager units cover the stage's pixels");
+static_assert(XP_UPT * XP_STAGERS / 4 >= XP_NPIX, "the stager units cover the stage's pixels");   // the 16 x 32 tile
 
 // Stager waves: half-steps k = (tile, 16-channel block cb16 = k % 4) in the MFMA waves' order; half-steps
 // 2i, 2i+1 make c-block step i (stage i & 1).  Two register sets of one half-step each are loaded
@@ -90,40 +110,43 @@ static_assert(XP_UPT * XP_STAGERS / 4 >= XP_NPIX, "the stager units cover the st
 // A unit's global and LDS offsets are tile-invariant: computed once; per half-step a wave-uniform
 // buffer descriptor at the tile's origin (loads outside the input take an offset past the records
 // and return the zero padding), and interior tiles skip the bound tests.
-template <bool IN_CB>
+// T::HANDOFF: drain(tile) stores the outputs of a finished tile from the hand-over buffer (tower_h16s.h has
+// the barrier protocol); it runs in the first c-block step of the next tile, after that step's loads are
+// issued, and for the workgroup's last tile after the loop.
+template <class T, bool IN_CB, typename DRAIN>
 __device__ __forceinline__ void h16_stager_loop(char *hsm, const float *__restrict__ in, int Hin, int Win,
                                                 const XpBatch &bt, int st, const float *__restrict__ in_amax,
-                                                const float *__restrict__ hdr)
+                                                const float *__restrict__ hdr, DRAIN &&drain)
 {
     const int tile0 = blockIdx.x, gstride = gridDim.x;
     const int nsteps = ((bt.ntiles - 1 - tile0) / gstride + 1) * H16_NCB;
     const int nh = 2 * nsteps;
-    uint32_t uoff[XP_UPT], uyx[XP_UPT], ulds[XP_UPT];
+    uint32_t uoff[T::UPT], uyx[T::UPT], ulds[T::UPT];
 #pragma unroll
-    for (int i = 0; i < XP_UPT; i++) {
+    for (int i = 0; i < T::UPT; i++) {
         const int u = h16_unit(st, i), px = u >> 2, chunk = u & 3;
-        const int iy = px / XP_IX, ix = px - iy * XP_IX;
-        const bool ok = u < XP_UNITS;
+        const int iy = px / T::IX, ix = px - iy * T::IX;
+        const bool ok = u < T::UNITS;
         uoff[i] = ok ? (uint32_t)((iy * Win + ix) * (IN_CB ? 64 : 256) + 16 * chunk) : XP_OOB;
         uyx[i] = ok ? (uint32_t)(iy << 16 | ix) : 0xFFFF0000u;
-        ulds[i] = ok ? (uint32_t)((chunk >> 1) * H16_PLANE + px * 16 + (chunk & 1) * 8) : 0u;
+        ulds[i] = ok ? (uint32_t)((chunk >> 1) * T::PLANE + px * 16 + (chunk & 1) * 8) : 0u;
     }
-    auto load = [&](float4 (&v)[XP_UPT], int k) {
+    auto load = [&](float4 (&v)[T::UPT], int k) {
         const int t = tile0 + (k >> 2) * gstride, cb16 = k & 3;
         int img, ty0, tx0;
-        xp_tile(bt, t, img, ty0, tx0);
+        h16_tile<T>(bt, t, img, ty0, tx0);
         const float *src = in + img * bt.in_stride;
         const __amdgpu_buffer_rsrc_t rs =
             xp_rsrc(IN_CB ? src + (((size_t)cb16 * Hin + ty0) * Win + tx0) * 16
                           : src + ((size_t)ty0 * Win + tx0) * 64 + cb16 * 16);
         const int ly = Hin - ty0, lx = Win - tx0;
-        if (ly >= XP_IY && lx >= XP_IX) {   // wave-uniform: the tile's input window is inside the input
+        if (ly >= T::IY && lx >= T::IX) {   // wave-uniform: the tile's input window is inside the input
 #pragma unroll
-            for (int i = 0; i < XP_UPT; i++)
+            for (int i = 0; i < T::UPT; i++)
                 v[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, uoff[i], 0, H16_ACT_AUX));
         } else {
 #pragma unroll
-            for (int i = 0; i < XP_UPT; i++) {
+            for (int i = 0; i < T::UPT; i++) {
                 const bool ok = (int)(uyx[i] >> 16) < ly && (int)(uyx[i] & 0xFFFFu) < lx;
                 v[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? uoff[i] : XP_OOB, 0, H16_ACT_AUX));
             }
@@ -131,19 +154,19 @@ __device__ __forceinline__ void h16_stager_loop(char *hsm, const float *__restri
     };
     int sc_img = -1;
     float s = 1.0f, unscale = 1.0f;
-    auto store = [&](const float4 (&v)[XP_UPT], int k) {
+    auto store = [&](const float4 (&v)[T::UPT], int k) {
         const int im = (tile0 + (k >> 2) * gstride) / bt.tiles_img;
         if (im != sc_img) {   // the tile's image changed: its bound word (tiles run image-major)
             xp_scales(false, in_amax + im * bt.amax_stride, hdr, s, unscale);
             sc_img = im;
         }
         // half h = k & 1 of the c-block: quarter planes 2h, 2h + 1
-        char *sb = hsm + ((k >> 1) & 1) * H16_STAGE + (k & 1) * 2 * H16_PLANE;
+        char *sb = hsm + ((k >> 1) & 1) * T::STAGE + (k & 1) * 2 * T::PLANE;
 #pragma unroll
-        for (int i = 0; i < XP_UPT; i++)
-            if (h16_unit(st, i) < XP_UNITS) h16_put(sb + ulds[i], v[i], s);
+        for (int i = 0; i < T::UPT; i++)
+            if (h16_unit(st, i) < T::UNITS) h16_put<T>(sb + ulds[i], v[i], s);
     };
-    float4 ra[XP_UPT], rb[XP_UPT];
+    float4 ra[T::UPT], rb[T::UPT];
     load(ra, 0);
     load(rb, 1);
     store(ra, 0);
@@ -159,8 +182,10 @@ __device__ __forceinline__ void h16_stager_loop(char *hsm, const float *__restri
         if (2 * i + 4 < nh) load(ra, 2 * i + 4);
         if (2 * i + 3 < nh) store(rb, 2 * i + 3);
         if (2 * i + 5 < nh) load(rb, 2 * i + 5);
+        if (T::HANDOFF && i >= 2 && !(i & 1)) drain(tile0 + ((i - 2) >> 1) * gstride);
         __syncthreads();
     }
+    if (T::HANDOFF) drain(tile0 + ((nsteps - 2) >> 1) * gstride);
 }
 
 // Stager waves, layer 2 (FIRST): the stage is conv1 (Cin = 1, 3x3, bias, ReLU; mc_cnn_brunch.py:31-48) of
@@ -351,12 +376,13 @@ struct H16B {
 };
 
 // B fragment of (tap, row r, pixel half ph); sb = the stage at the lane's base.
+template <class T = H16T32>
 __device__ __forceinline__ H16B h16_bfrag_at(const char *sb, int tap, int r, int ph)
 {
-    const int off = ((r + tap / 3) * XP_IX + 16 * ph + tap % 3) * 16;
+    const int off = ((r + tap / 3) * T::IX + 16 * ph + tap % 3) * 16;
     H16B f;
     f.hi = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(sb + off));
-    f.lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(sb + 4 * H16_PLANE + off));
+    f.lo = __builtin_bit_cast(f16x8, *reinterpret_cast<const uint4 *>(sb + 4 * T::PLANE + off));
     return f;
 }
 // ... of step b = (half-tap b >> 3, row (b >> 1) & 3, pixel half b & 1)
@@ -658,9 +684,10 @@ __global__ __launch_bounds__(512) void conv64_h16_kernel(const float *__restrict
     if (tile >= bt.ntiles) return;
     const float *hdr = wkblob + LK_F16 + LK_W;
     if (wave >= 4) {
+        auto nodrain = [](int) {};
         if (FIRST) h16_conv1_stager_loop(hsm, in, Hin, Win, bt, tid - XP_STAGERS, in_amax, hdr, w1blob);
         else if (ISPL) h16_dma_stager_loop(hsm, in, Hin, Win, bt, tid - XP_STAGERS);
-        else h16_stager_loop<IN_CB>(hsm, in, Hin, Win, bt, tid - XP_STAGERS, in_amax, hdr);
+        else h16_stager_loop<H16T32, IN_CB>(hsm, in, Hin, Win, bt, tid - XP_STAGERS, in_amax, hdr, nodrain);
         return;
     }
     if (OSPL) xp_publish_scale(FIRST, bt, in_amax, hdr, out_amax);

@@ -26,6 +26,7 @@ struct TowerLaunch {
 __attribute__((visibility("hidden"))) void launch_fp32(const TowerLaunch &L);
 __attribute__((visibility("hidden"))) void launch_x6p(const TowerLaunch &L);
 __attribute__((visibility("hidden"))) void launch_h16(const TowerLaunch &L);   // conv64_h16_kernel, conv64_h16q_kernel
+__attribute__((visibility("hidden"))) void launch_h16s(const TowerLaunch &L);  // conv64_h16s_kernel (16 x 16 tiles)
 __attribute__((visibility("hidden"))) void launch_wino(const TowerLaunch &L);
 
 }  // namespace sde

@@ -56,12 +56,12 @@ def tower_steps(img_pad, packed, nlayers: int, out, ws, precision: str = "f16x3"
     # between layers: what sde_tower_forward_batch passes -- split activations on the f16x3 tower when
     # built with them (ops.TOWER_SPLIT_ACT; <= 32 layers, < 2^24 pixels), else c-block-major fp32
     sp = ops.TOWER_SPLIT_ACT and precision == "f16x3" and 2 < L <= ops.SCALE_WORD and h2 * w2 < SPLIT_MAX_PIX
-    cbl = not sp and precision in ("bf16x6", "f16x3", "f16x3w", "f16x3m32")
+    cbl = not sp and precision in ("bf16x6", "f16x3", "f16x3w", "f16x3m32", "f16x3t32")
     act = h2 * w2 * nf if L > 2 else 0
     wsf = ws[: 2 * N * act * 4 + N * AMAX_WORDS * 4].view(torch.float32)
     bufs = [wsf[: N * act], wsf[N * act: 2 * N * act]]
     words = wsf[2 * N * act:].view(N, AMAX_WORDS)
-    f16 = precision in ("f16x3", "f16x3w", "f16x3m32")
+    f16 = precision in ("f16x3", "f16x3w", "f16x3m32", "f16x3t32")
     if f16:
         words.zero_()
         ops.absmax_batch(img_pad, words)

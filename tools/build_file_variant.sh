@@ -2,6 +2,7 @@
 # usage: bash tools/build_file_variant.sh FILE.hip NAME [hipcc flags...]
 #        SRC=path/to/other.hip bash tools/build_file_variant.sh FILE.hip NAME ...  (FILE.hip replaced by SRC)
 # The tower is one file per kernel family: tower_h16.hip takes -DSDE_H16_HEADER=... (a probe copy of tower_h16.h),
+# tower_h16s.hip -DSDE_H16S_HEADER=... (tower_h16.h + tower_h16s.h, tools/variants/make_phase_header.py),
 # tower.hip -DSDE_SPLIT_ACT=1; tower_x6p.hip, tower_wino.hip and tower_fp32.hip hold the other families.
 # An SGM variant rebuilds sgm.hip (it includes sgm_scan.h, sgm_faithful.h and sgm_wave.h): ... sgm.hip sgm_NAME;
 # the post-processing kernels are postprocess.hip.
