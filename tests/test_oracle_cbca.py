@@ -5,6 +5,7 @@ CBCA is BUILD-DEFINED: the reference has none -- parity unp
 import numpy as np
 import pytest
 
+import cbca_cases as cc
 from oracle import oracle
 
 
@@ -123,6 +124,94 @@ def test_cbca_segments_match_literal(side, H, W):
     cv = (rng.standard_normal((H, W, D)) * 3 + 20).astype(np.float32)   # far from 0: rounding matters
     got = oracle.cbca(cv, ref, oth, side, 1, L1=6)
     assert got.tobytes() == cbca_literal(cv, ref, oth, side, 1, 6).tobytes()
+
+
+@pytest.mark.parametrize("side", ["left", "right"])
+@pytest.mark.parametrize("kind", ["nan", "inf", "nan_invalid"])
+def test_cbca_nonfinite_matches_literal(kind, side):
+    """A NaN or an inf poisons its chain from its position to the end of that chain, an invalid voxel (left
+    coordinate q < d) is on no chain: the C loops and the voxel-by-voxel statement agree on the footprint."""
+    rng = np.random.default_rng(13)
+    H, W, D = 7, 11, 5
+    il, ir = _images(rng, H, W), _images(rng, H, W)
+    al, ar = oracle.cbca_arms(il, 5, 0.03), oracle.cbca_arms(ir, 5, 0.03)
+    ref, oth = (al, ar) if side == "left" else (ar, al)
+    cv = (rng.standard_normal((H, W, D)) * 3 + 20).astype(np.float32)
+    q = 1 if kind == "nan_invalid" else 5                     # left coordinate of the poisoned voxel, d = 3
+    x = q if side == "left" else (q - 3) % W
+    cv[3, x, 3] = np.inf if kind == "inf" else np.nan
+    if kind == "inf":
+        cv[2, 4, 1] = -np.inf
+    want = cbca_literal(cv, ref, oth, side, 2, 5)
+    got = oracle.cbca(cv, ref, oth, side, 2, L1=5)
+    assert cc.same_f32(got, want)
+    assert np.isfinite(want).any()
+    if kind == "nan_invalid":
+        assert np.isnan(want).sum() == 1 and np.isnan(want[3, x, 3])
+    else:
+        assert np.isnan(want).sum() > 1
+
+
+@pytest.mark.parametrize("H,W,L1", [(6, 300, 32), (290, 6, 16)])
+def test_cbca_full_arms_segments_match_literal(H, W, L1):
+    """Flat image: every arm reaches min(L1 - 1, distance to the border), across a segment seam."""
+    rng = np.random.default_rng(17)
+    D = 3
+    arms = oracle.cbca_arms(np.zeros((H, W), np.float32), L1, 1.0)
+    assert int((arms & 255).max()) == min(L1 - 1, W - 1) and int((arms >> 24).max()) == min(L1 - 1, H - 1)
+    cv = (rng.standard_normal((H, W, D)) * 3 + 20).astype(np.float32)
+    got = oracle.cbca(cv, arms, arms, "left", 1, L1=L1)
+    assert got.tobytes() == cbca_literal(cv, arms, arms, "left", 1, L1).tobytes()
+
+
+@pytest.mark.parametrize("H,W,D,L1", cc.BOX_CASES)
+def test_box_expected_matches_oracle(H, W, D, L1):
+    """The closed form of the box-filter cases (integer costs: exact in fp64 wherever chains restart)."""
+    cv, want = cc.box_case(H, W, D, L1)
+    arms = oracle.cbca_arms(np.zeros((H, W), np.float32), L1, 1.0)
+    got = oracle.cbca(cv, arms, arms, "left", 1, L1=L1)
+    assert got.tobytes() == want.tobytes()
+    assert (want != cv).any()
+
+
+def test_box_expected_by_hand():
+    """3 x 3 x 2, M = 1: window sums and counts written out."""
+    cv = np.arange(18, dtype=np.float32).reshape(3, 3, 2) - 8
+    out = cc.box_expected(cv, 1)
+    assert out[0, 0, 1] == cv[0, 0, 1] and out[2, 0, 1] == cv[2, 0, 1]          # invalid: x < d
+    # d = 0, centre: all 9 voxels; corner (0, 0): rows 0..1 x columns 0..1
+    assert out[1, 1, 0] == np.float32(float(cv[:, :, 0].sum()) * (1.0 / 9.0))
+    assert out[0, 0, 0] == np.float32(float(cv[:2, :2, 0].sum()) * (1.0 / 4.0))
+    # d = 1, column 1: its left arm is cut at the first valid column 1 (window columns 1..2), all 3 rows
+    assert out[1, 1, 1] == np.float32(float(cv[:, 1:, 1].sum()) * (1.0 / 6.0))
+
+
+def test_plateau_images_reach_every_arm():
+    """The generator's promise at the shapes it was checked for, seed 1, in all four directions where both axes are
+    long enough; the 3-pixel runs of _images never give a vertical support arm beyond a few pixels."""
+    for (H, W), L1 in (((70, 70), 14), ((300, 70), 16), ((560, 70), 32)):
+        assert (H, W, L1 - 1) not in cc.PLATEAU_SEEDS
+        il, ir = cc.plateau_images(H, W, L1 - 1)
+        al, ar = oracle.cbca_arms(il, L1, cc.TAU), oracle.cbca_arms(ir, L1, cc.TAU)
+        assert cc.line_covered(al, ar, "h", L1 - 1) and cc.line_covered(al, ar, "v", L1 - 1)
+        cov = cc.arm_coverage(al, ar, W, cc.COVER_DS)
+        assert all(cov[k] == set(range(L1)) for k in cc.DIRS)
+    rng = np.random.default_rng(1)
+    il, ir = _images(rng, 70, 70), _images(rng, 70, 70)
+    al, ar = oracle.cbca_arms(il, 32, 0.03), oracle.cbca_arms(ir, 32, 0.03)
+    cov = cc.arm_coverage(al, ar, 70, cc.COVER_DS)
+    assert max(cov["u"]) < 13 and not cc.line_covered(al, ar, "h", 31)
+
+
+def test_same_f32():
+    a = np.array([1.0, np.nan, np.inf, -np.inf, 0.0], np.float32)
+    b = a.copy()
+    b.view(np.uint32)[1] ^= 1 << 31                  # another NaN payload
+    assert cc.same_f32(a, b)
+    b[4] = -0.0
+    assert not cc.same_f32(a, b)
+    assert not cc.same_f32(a, np.array([1.0, 7.0, np.inf, -np.inf, 0.0], np.float32))
+    assert not cc.same_f32(a, np.array([1.0, np.nan, np.finfo(np.float32).max, -np.inf, 0.0], np.float32))
 
 
 def _shear(cl):
