@@ -452,6 +452,58 @@ int sde_lrc_fill(const float *disp_l, const uint8_t *lrc_l, int H, int W, float 
 int sde_median5(const float *src, int H, int W, float *dst, void *stream);
 
 /* ---------------------------------------------------------------------- */
+/* Sub-pixel disparities and the 9x9 bilateral filter: the two stages the    */
+/* reference carries switched off (process_functional.py:813-819, :830-836;  */
+/* :882-974 with its call commented out at :1260).  Additive in ABI 4.      */
+/* ---------------------------------------------------------------------- */
+/*
+ * The parabola step refine(i, lo, hi, c-, c0, c+): i the integer winner, c-, c0, c+ the float32 costs at i - 1,
+ * i, i + 1.  The result is float32(i) unless lo < i < hi - 1, the three costs are finite and den > 0; then, with
+ * Numba's promotion of `index - (c_ - _c)/(2*(_c + c_ - 2*c))` (:818) and every operation rounded to nearest on
+ * its own (nothing fused):
+ *   num = float32(c+ - c-);  s = float32(c- + c+);          float32 subtraction and addition
+ *   den = 2.0 * ((double)s - 2.0 * (double)c0);             float64
+ *   result = float32((double)i - (double)num / den)         float64 division and subtraction, one rounding
+ * The three guards are the only departures from the reference's dead code, which would produce inf or NaN
+ * without them.  There is no clamp: with costs a few ulps apart the offset can exceed 0.5 (costs [2, c+5u, c, c, 3]
+ * at c = 1, u = ulp(c) give 2.625).
+ */
+
+/*
+ * sde_wta followed by the parabola step on the stored volume: i is exactly sde_wta's winner for the same
+ * (layout, rule), lo = 0, hi = D, and the three costs are read from the volume as they stand.  A pixel without a
+ * winner keeps -1.0f.  Argument checks are sde_wta's.
+ */
+int sde_wta_subpixel(const float *vol, int H, int W, int D, int layout, int rule, float *disp, void *stream);
+
+/*
+ * The parabola step for the fused cost volume + WTA (sde_cv_wta / sde_cv_wta_right), which store no volume: a
+ * pixel of disp_in that is not an integer in [d0, d1) is copied through bit for bit (-1 and NaN included);
+ * otherwise i is that integer, lo = d0, hi = d1 and the three costs are the values
+ * sde_cost_volume(..., SDE_LAYOUT_DHW) holds, recomputed in its exact arithmetic:
+ *   side = SDE_SIDE_LEFT:  x - d >= 0 ? cost(x, d)     : -0.0f
+ *   side = SDE_SIDE_RIGHT: x + d <  W ? cost(x + d, d) : -0.0f      (sde_cv_wta_right's indexing)
+ * So on sde_cv_wta's map over [0, D) it equals sde_wta_subpixel of the stored DHW volume, by bytes.  fl / fr:
+ * the [H][W][C] maps sde_cv_wta takes; disp_out == disp_in is allowed (each pixel reads only itself).
+ * SDE_ERR_ARG: a null pointer, H, W or C < 1, d0 < 0, d1 <= d0, d1 > 2^24, side not exactly one of the two.
+ */
+int sde_cv_subpixel(const float *fl, const float *fr, int H, int W, int C, int d0, int d1, int side,
+                    const float *disp_in, float *disp_out, void *stream);
+
+/*
+ * Bilateral_Filter_kernel (process_functional.py:882-974) for one view: img_u8 / src / dst [H][W], dst != src,
+ * every pixel of dst written.  For pixel (y, x), with wsum = dsum = 0.0 in float64 and for i = -4..4 (outer),
+ * j = -4..4 (inner): I' = img[y+i][x+j], d' = src[y+i][x+j], both 0 outside the image (the reference's
+ * zero-padded tile); a = |int(img[y][x]) - int(I')|; if a < 5: w = float32(weights[a]) with the reference's
+ * literals 0.167747, 0.165145, 0.157581, 0.145735, 0.130632 (:920-924; entries 5..9 are unreachable),
+ * wsum += (double)w, dsum += (double)float32(w * d').  dst = float32(dsum / wsum).  The sequential order is part
+ * of the definition; the centre tap always counts, so wsum > 0; non-finite disparities propagate as the
+ * arithmetic says.  The reference's staging overrun (`id + 512 < 596`, :939) touches no value that is read and is
+ * not reproduced.  H <= 16 * 65535.
+ */
+int sde_bilateral9(const uint8_t *img_u8, const float *src, int H, int W, float *dst, void *stream);
+
+/* ---------------------------------------------------------------------- */
 /* Local matcher (local_mathod.py): SAD+SSD, rank and census.  It needs no   */
 /* weights: two uint8 images in, disparity maps out.  Additive in ABI 4.    */
 /* ---------------------------------------------------------------------- */

@@ -93,6 +93,10 @@ SIGNATURES = {
     "sde_lr_consistency": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "sde_lrc_fill": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sde_median5": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "sde_wta_subpixel": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sde_cv_subpixel": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p]),
+    "sde_bilateral9": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "sde_census_transform": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sde_rank_transform": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "sde_census_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),

@@ -1,13 +1,16 @@
 """Drop-in for the reference's match.py batch entry point (match.py:19-103).
 
     python -m scenedepthestimation_amd.match [-g GPUS] [--checkpoint PATH|synthetic] [--cpu-path]
+           [--subpixel] [--bilateral]
 
 Loops over ``./test/left_{i}.jpg`` / ``right_{i}.jpg`` for i = 1..18 (match.py:46),
 builds the tower once (weights packed and uploaded once, like the single TF
 graph of match.py:34-37), and writes ``./disparity/ld{i}.png`` as
 ``uint8(disparity) * 2`` (match.py:90).  ``detail_time`` accumulates per-stage
 seconds as in match.py:71-75 and is printed at the end (the reference's print is
-commented out, match.py:95-103).
+commented out, match.py:95-103).  --subpixel / --bilateral switch on the parabola refinement and the 9x9
+bilateral filter the reference carries commented out (process_functional.py:813-819, :882-974); --bilateral
+belongs to the SGM path (it filters the median's output).
 
 Multi-GPU (new; the reference has none): under torchrun every rank takes pairs
 i = rank+1, rank+1+N, ... (pair data-parallel, no collective).
@@ -34,11 +37,17 @@ def build_parser():
     p.add_argument("--pairs", type=int, default=18, help="number of pairs (match.py:46 uses 1..18)")
     p.add_argument("--image-path", type=str, default="./test/")
     p.add_argument("--out-path", type=str, default="./disparity/")
+    p.add_argument("--subpixel", action="store_true", help="parabola refinement of the winner (off in the reference)")
+    p.add_argument("--bilateral", action="store_true",
+                   help="9x9 bilateral filter after the median (off in the reference; SGM path only)")
     return p
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.bilateral and args.cpu_path:
+        parser.error("--bilateral filters the median's output: it belongs to the SGM path")
     if "WORLD_SIZE" not in os.environ:
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu     # match.py:24 (CUDA_VISIBLE_DEVICES)
     import torch
@@ -59,7 +68,8 @@ def main(argv=None):
             raise AttributeError(f"'NoneType' object has no attribute 'astype' (cannot read {lp} / {rp})")
         H, W = _l.shape
         if matcher is None or (matcher.H, matcher.W) != (H, W):
-            matcher = StereoMatcher(H, W, args.ndisp, weights=weights)
+            matcher = StereoMatcher(H, W, args.ndisp, weights=weights, subpixel=args.subpixel,
+                                    bilateral=args.bilateral)
         import time
         t0 = time.time()
         for k, img in enumerate((_l, _r)):
@@ -71,7 +81,10 @@ def main(argv=None):
         torch.cuda.synchronize()
         detail_time[0] += time.time() - t0
         if args.cpu_path:
-            disp = ops.cv_wta(fl, fr, 0, args.ndisp)[0].cpu().numpy()
+            disp = ops.cv_wta(fl, fr, 0, args.ndisp)[0]
+            if args.subpixel:
+                ops.cv_subpixel(fl, fr, 0, args.ndisp, disp, "left", out=disp)
+            disp = disp.cpu().numpy()
         else:
             # disparity_compute_by_gpu (match.py:85) on the device-resident features: no host round trip
             matcher.load_images(_l, _r)

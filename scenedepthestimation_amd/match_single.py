@@ -2,6 +2,7 @@
 
     python -m scenedepthestimation_amd.match_single [-g GPU] [-i ID] [-f FILE]
            [--checkpoint PATH|synthetic] [--cpu-path [--lr-check]] [--ndisp N] [--ui]
+           [--subpixel] [--bilateral]
 
 Same flags, paths and outputs as match_single.py:15-57 (and, with --ui,
 match_single_ui.py:20-58): reads ``./eval/left_{id}.png`` / ``right_{id}.png``
@@ -16,6 +17,11 @@ the fused GPU kernel, bit-identical to the NumPy path.  --lr-check (with --cpu-p
 only) writes that path's left map after the reference's post-processing instead
 (StereoMatcher.match_lr: the right view's map, the left-right check, LRC fill and
 the 5x5 median of process_functional.py:977-1088, :840-879).
+
+--subpixel and --bilateral switch on the two stages the reference carries commented out: the parabola step
+on the winner's two neighbours (process_functional.py:813-819) and the 9x9 bilateral filter of the median's
+output (:882-974).  Both are off by default; --bilateral needs a path that has a median (the SGM path or
+--cpu-path --lr-check).  The written PNG is still ``uint8(disparity)``.
 """
 from __future__ import annotations
 
@@ -42,6 +48,10 @@ def build_parser(ui: bool = False):
                    help="with --cpu-path: left-right check, LRC fill and 5x5 median on the fused kernels' two views")
     p.add_argument("--ndisp", type=int, default=128, help="disparity range (the reference hard-codes 128)")
     p.add_argument("--ui", action="store_true", default=ui, help="match_single_ui.py paths and x2 output scaling")
+    p.add_argument("--subpixel", action="store_true",
+                   help="parabola refinement of the winner (process_functional.py:813-819, off in the reference)")
+    p.add_argument("--bilateral", action="store_true",
+                   help="9x9 bilateral filter after the median (process_functional.py:882-974, off in the reference)")
     return p
 
 
@@ -56,19 +66,25 @@ def parse_args(argv=None, ui: bool = False):
     args = p.parse_args(argv)
     if args.lr_check and not args.cpu_path:
         p.error("--lr-check needs --cpu-path (the SGM path has its own left-right check)")
+    if args.bilateral and args.cpu_path and not args.lr_check:
+        p.error("--bilateral filters the median's output: use the SGM path or --cpu-path --lr-check")
     return args
 
 
-def lr_checked_disparity(left, right, ndisp, checkpoint):
+def lr_checked_disparity(left, right, ndisp, checkpoint, subpixel=False, bilateral=False, left_u8=None):
     """The --lr-check map: compute_feature's tower on the normalised images (the same padded input, so the same
-    features as the plain --cpu-path run), then StereoMatcher.lr_checked on them."""
+    features as the plain --cpu-path run), then StereoMatcher.lr_checked on them.  bilateral=True needs the left
+    u8 image (the filter's intensities)."""
     import torch
 
     from . import mc_cnn
     from .pipeline import StereoMatcher
     nlayers = 11 // 2
     H, W = left.shape[:2]
-    m = StereoMatcher(H, W, ndisp, weights=mc_cnn.load_weights(checkpoint, nlayers), nlayers=nlayers)
+    m = StereoMatcher(H, W, ndisp, weights=mc_cnn.load_weights(checkpoint, nlayers), nlayers=nlayers,
+                      subpixel=subpixel, bilateral=bilateral)
+    if bilateral:
+        m.img_u8[0].copy_(torch.from_numpy(np.ascontiguousarray(left_u8, np.uint8)))
     for i, img in enumerate((left, right)):
         buf = np.zeros((H + 2 * nlayers, W + 2 * nlayers), np.float32)
         buf[nlayers:nlayers + H, nlayers:nlayers + W] = img[..., 0]
@@ -95,15 +111,24 @@ def run(args) -> str:
         raise AttributeError(f"'NoneType' object has no attribute 'astype' (cannot read {lp} / {rp})")
     left = normalise(_left.astype(np.float32))
     right = normalise(_right.astype(np.float32))
+    subpixel, bilateral = getattr(args, "subpixel", False), getattr(args, "bilateral", False)
     if args.cpu_path and getattr(args, "lr_check", False):
-        disp = lr_checked_disparity(left, right, args.ndisp, args.checkpoint)
+        disp = lr_checked_disparity(left, right, args.ndisp, args.checkpoint, subpixel, bilateral, _left)
     else:
         fl, fr = compute_feature(left, right, 11, 11, 64, args.checkpoint)
-        if args.cpu_path:
+        if args.cpu_path and subpixel:
+            import torch
+
+            from . import ops
+            vol = torch.from_numpy(compute_cost_volume(fl, fr, args.ndisp)).cuda()
+            disp = ops.wta_subpixel(vol, "DHW", "inf").cpu().numpy()
+            assert (disp >= 0).all()          # as WTA1 (:109)
+        elif args.cpu_path:
             disp = WTA1(compute_cost_volume(fl, fr, args.ndisp))
         else:
             detail_time = np.zeros(shape=[7], dtype=np.float32)
-            disp, _, detail_time = disparity_compute_by_gpu(_left, _right, fl, fr, detail_time, ndisp=args.ndisp)
+            disp, _, detail_time = disparity_compute_by_gpu(_left, _right, fl, fr, detail_time, ndisp=args.ndisp,
+                                                            subpixel=subpixel, bilateral=bilateral)
     out = disp.astype("uint8") * 2 if args.ui else disp.astype("uint8")
     path = "./result/{}/ld{}.png".format(args.file, args.id)
     imageio.imwrite(path, out)

@@ -690,6 +690,62 @@ def median5(src, dst):
 
 
 # ----------------------------------------------------------------------------
+# Sub-pixel disparities and the 9x9 bilateral filter (process_functional.py:813-819, :882-974; both switched off in
+# the reference; definitions in include/sde.h)
+# ----------------------------------------------------------------------------
+SIDES = {"left": SDE_SIDE_LEFT, "right": SDE_SIDE_RIGHT}
+
+
+def wta_subpixel(vol, layout: str = "DHW", rule: str = "inf", out=None):
+    """wta(vol, layout, rule) followed by the parabola step on the winner's two neighbours in the stored volume
+    (sde_wta_subpixel): a winner at d = 0 or D - 1, a non-finite neighbour, a parabola that is not convex and a
+    pixel without a winner (-1) keep the integer."""
+    if vol.dim() != 3:
+        raise ValueError("volume must be 3-D")
+    if layout == "DHW":
+        D, H, W = vol.shape
+    else:
+        H, W, D = vol.shape
+    pv = _need(vol, "volume")
+    if out is None:
+        out = _empty((H, W), torch.float32, vol)
+    po = _need(out, "disp", shape=(H, W))
+    check(lib.sde_wta_subpixel(pv, H, W, D, LAYOUTS[layout], RULES[rule], po, _stream()), "sde_wta_subpixel")
+    return out
+
+
+def cv_subpixel(fl, fr, d0: int, d1: int, disp, side: str = "left", out=None):
+    """The parabola step on a map of cv_wta (side 'left') or cv_wta_right ('right') over [d0, d1), whose volume was
+    never stored: the three costs around every integer pixel of `disp` are recomputed in the cost volume's exact
+    arithmetic (sde_cv_subpixel), so the result equals wta_subpixel of the stored DHW volume.  Anything that is
+    not an integer in [d0, d1) is copied through.  out may be `disp` itself (in place); a new map when None."""
+    pl, pr, H, W, C = _feat_pair(fl, fr)
+    if side not in SIDES:
+        raise ValueError(f"side must be 'left' or 'right' (got {side!r})")
+    pi = _need(disp, "disp", shape=(H, W))
+    if out is None:
+        out = _empty((H, W), torch.float32, fl)
+    po = _need(out, "out", shape=(H, W))
+    check(lib.sde_cv_subpixel(pl, pr, H, W, C, int(d0), int(d1), SIDES[side], pi, po, _stream()), "sde_cv_subpixel")
+    return out
+
+
+def bilateral9(img_u8, src, out=None):
+    """Bilateral_Filter_kernel (process_functional.py:882-974) for one view: the 9x9 window of `src` f32 [H,W]
+    weighted by the intensity difference in img_u8 [H,W] (taps with a difference of 5 or more are rejected, zero
+    padding outside the image) -> f32 [H,W], every pixel written; out must not be src (sde_bilateral9)."""
+    if img_u8.dim() != 2:
+        raise ValueError("image must be a uint8 [H,W] tensor")
+    H, W = img_u8.shape
+    pi = _need(img_u8, "image", dtype=torch.uint8)
+    ps = _need(src, "src", shape=(H, W))
+    if out is None:
+        out = _empty((H, W), torch.float32, src)
+    check(lib.sde_bilateral9(pi, ps, H, W, _need(out, "out", shape=(H, W)), _stream()), "sde_bilateral9")
+    return out
+
+
+# ----------------------------------------------------------------------------
 # Local matcher: SAD+SSD, rank and census (local_mathod.py:13-165; definitions in include/sde.h)
 # ----------------------------------------------------------------------------
 LOCAL_INVALID = _lib.SDE_LOCAL_INVALID

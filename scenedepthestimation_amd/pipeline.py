@@ -104,8 +104,12 @@ class StereoMatcher:
     def __init__(self, height: int, width: int, ndisp: int, weights=None, nlayers: int = 5,
                  nf: int = 64, device=None, d_range=None, sgm: bool = False, tower_precision: str = "f16x3",
                  cv_mode: str = "certified", cbca_iters: int = 0, cbca_L1: int = 14, cbca_tau: float = 0.02,
-                 emit_split: bool = False, sgm_placement_trials: int = SGM_PLACEMENT_TRIALS):
+                 emit_split: bool = False, sgm_placement_trials: int = SGM_PLACEMENT_TRIALS,
+                 subpixel: bool = False, bilateral: bool = False):
         self.H, self.W, self.D = int(height), int(width), int(ndisp)
+        # the two stages the reference carries switched off (process_functional.py:813-819, :882-974); off by
+        # default, and with both off every call below makes the launches it made before they existed
+        self.subpixel, self.bilateral = bool(subpixel), bool(bilateral)
         # cross-based aggregation before SGM (build-defined stage; 0 = the reference's GPU path)
         self.cbca_iters, self.cbca_L1, self.cbca_tau = int(cbca_iters), int(cbca_L1), float(cbca_tau)
         self.nlayers, self.nf = int(nlayers), int(nf)
@@ -116,6 +120,11 @@ class StereoMatcher:
         self.tower_precision = tower_precision
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.d0, self.d1 = (0, self.D) if d_range is None else (int(d_range[0]), int(d_range[1]))
+        if self.subpixel and (self.d0, self.d1) != (0, self.D):
+            # a shard's winner may sit at the shard's end with its neighbour in the next shard; refine the
+            # merged map instead (ops.cv_subpixel over the whole range)
+            raise ValueError(f"subpixel=True needs the whole disparity range [0, {self.D}); this matcher holds "
+                             f"the shard [{self.d0}, {self.d1})")
         w = mc_cnn.load_weights(weights, self.nlayers)
         hw, hb = mc_cnn.layer_lists(w, self.nlayers)
         packed = ops.pack_tower_weights(hw, hb)
@@ -210,9 +219,12 @@ class StereoMatcher:
                           mode=self.cv_mode, workspace=self.cv_ws)
 
     def match(self):
-        """One pass of the hot path on the resident images: features + fused CV/WTA -> disparity."""
+        """One pass of the hot path on the resident images: features + fused CV/WTA -> disparity; with
+        subpixel=True followed by the parabola step on the winner's recomputed neighbours (ops.cv_subpixel)."""
         self.features()
         self.cost_wta()
+        if self.subpixel:
+            ops.cv_subpixel(self.feat[0], self.feat[1], self.d0, self.d1, self.disp, "left", out=self.disp)
         return self.disp
 
     # -- left-right-checked fast path ------------------------------------------
@@ -227,6 +239,8 @@ class StereoMatcher:
             self.argmin_r = torch.empty((H, W), dtype=torch.int32, device=dev)
             self.cv_ws_r = torch.empty(ops.cv_wta_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
             self.lr_bufs = dict(lrc=[u8(), u8()], filled=f32(), checked=f32())
+            if self.bilateral:
+                self.lr_bufs["smoothed"] = f32()
         return self.lr_bufs
 
     def cost_wta_right(self, want=("disp",)):
@@ -246,24 +260,34 @@ class StereoMatcher:
                              f"matcher holds the shard [{self.d0}, {self.d1})")
 
     def lr_checked(self, max_diff: float = 1.0):
-        """match_lr's stages after the features, on the features this matcher currently holds."""
+        """match_lr's stages after the features, on the features this matcher currently holds.  subpixel=True
+        refines both views' raw maps before the check; bilateral=True filters the median's output with the left
+        image (the reference's dead call, :1260, would filter the LRC-filled map and overwrite the median's
+        result: a documented divergence)."""
         self._need_whole_range()
         b = self._lr_bufs()
         self.cost_wta()
         self.cost_wta_right()
+        if self.subpixel:
+            ops.cv_subpixel(self.feat[0], self.feat[1], self.d0, self.d1, self.disp, "left", out=self.disp)
+            ops.cv_subpixel(self.feat[0], self.feat[1], self.d0, self.d1, self.disp_r, "right", out=self.disp_r)
         ops.lr_consistency(self.disp, self.disp_r, max_diff, b["lrc"][0], b["lrc"][1])
         ops.lrc_fill(self.disp, b["lrc"][0], out=b["filled"])
         # the 5x5 median of the filled map into the interior of a copy of it: the 2-pixel border keeps the
         # filled values
         b["checked"].copy_(b["filled"])
         ops.median5(b["filled"], b["checked"])
+        if self.bilateral:
+            ops.bilateral9(self.img_u8[0], b["checked"], out=b["smoothed"])
+            return b["smoothed"], self.disp_r, b["lrc"][0]
         return b["checked"], self.disp_r, b["lrc"][0]
 
     def match_lr(self, max_diff: float = 1.0):
         """The hot path with the reference's post-processing (is_error_match / LRC / median,
         process_functional.py:977-1088, :840-879) on both views' raw maps: features, cost_wta, cost_wta_right,
         the wrap-free left-right check, LRC fill of the left map, 5x5 median.  Returns (disp_l_checked, disp_r,
-        lrc_l); self.disp keeps the raw left map.  Not for a disparity shard (ValueError)."""
+        lrc_l); self.disp keeps the raw left map (refined with subpixel=True).  Not for a disparity shard
+        (ValueError)."""
         self._need_whole_range()
         self.features()
         return self.lr_checked(max_diff)
@@ -370,7 +394,9 @@ class StereoMatcher:
         return cv_l, cv_r
 
     def sgm_path(self, fl=None, fr=None, img_l=None, img_r=None, timings=None, post=True):
-        """process_functional.py:1093-1267 on device tensors; returns (disp_l, disp_r).
+        """process_functional.py:1093-1267 on device tensors; returns (disp_l, disp_r).  subpixel=True: the
+        unfused SGM pair followed by ops.wta_subpixel per side instead of the fused last direction;
+        bilateral=True: the 9x9 bilateral filter of each median-filtered map with its own image.
 
         timings: optional dict receiving per-stage seconds (synchronised)."""
         import time
@@ -404,8 +430,16 @@ class StereoMatcher:
         # both sides per launch (the reference's k loop); S := 8-path sum, no zero-fill pass
         # penalties from sgm_penalties (channels 0/1 zero), finite costs: DU folds into UD;
         # WTA_and_SupixelRefinement_kernel (:800-837) fused into the last direction
-        ops.sgm_8path_wta_pair(b["cv"][0], b["pen"][0], b["S"][0], b["disp"][0], b["cv"][1], b["pen"][1],
-                               b["S"][1], b["disp"][1], zero_du_penalties=True)
+        if self.subpixel:
+            # the parabola step needs the final S around the winner, which the fused last direction never
+            # stores: the unfused pair (S written in full), then WTA + refinement per side
+            ops.sgm_8path_pair(b["cv"][0], b["pen"][0], b["S"][0], b["cv"][1], b["pen"][1], b["S"][1],
+                               zero_du_penalties=True)
+            ops.wta_subpixel(b["S"][0], "HWD", "d0", out=b["disp"][0])
+            ops.wta_subpixel(b["S"][1], "HWD", "d0", out=b["disp"][1])
+        else:
+            ops.sgm_8path_wta_pair(b["cv"][0], b["pen"][0], b["S"][0], b["disp"][0], b["cv"][1], b["pen"][1],
+                                   b["S"][1], b["disp"][1], zero_du_penalties=True)
         t = mark("sgm", t)
         if not post:
             return b["disp"][0], b["disp"][1]
@@ -422,5 +456,13 @@ class StereoMatcher:
         disp_r_src.copy_(b["disp"][1])
         ops.median5(b["disp_a"], b["disp"][0])
         ops.median5(disp_r_src, b["disp"][1])
+        if self.bilateral:
+            # Bilateral_Filter_kernel (:882-974) of the median's output, each map with its own image, into the
+            # two maps the median has finished reading.  The reference's dead call (:1260) would filter the
+            # LRC-filled map and overwrite the median's result (documented divergence).
+            ops.bilateral9(img_l, b["disp"][0], out=b["disp_a"])
+            ops.bilateral9(img_r, b["disp"][1], out=b["disp_b"])
+            mark("filter", t)
+            return b["disp_a"], b["disp_b"]
         mark("filter", t)
         return b["disp"][0], b["disp"][1]

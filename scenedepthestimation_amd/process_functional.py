@@ -92,13 +92,16 @@ def WTA1(left_cost_volume):
     return _checked(ops.wta(_to_dev(left_cost_volume), layout="DHW", rule="inf"))
 
 
-def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, ndisp=128):
+def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, ndisp=128, subpixel=False,
+                             bilateral=False):
     """GPU path (process_functional.py:1093-1267): cost volume [H,W,D] (L, R; 1.0 fill),
     SGM penalties, 8-path SGM, WTA, LR check + LRC fill, 5x5 median.
 
     Returns (disparity_left, disparity_right, detail_time); detail_time slots as the
     reference: [1] cost volume, [3] SGM, [4] WTA, [5] LR check, [6] filtering (seconds).
-    ``ndisp`` defaults to the reference's hard-coded 128 (:1111).
+    ``ndisp`` defaults to the reference's hard-coded 128 (:1111).  ``subpixel`` / ``bilateral`` switch on the two
+    stages the reference carries commented out: the parabola step of the WTA kernel (:813-819) and
+    Bilateral_Filter_kernel (:882-974), the latter applied to the median's output.
     """
     assert imagel.shape == imager.shape                   # :1097
     H, W = imagel.shape[0:2]
@@ -111,6 +114,7 @@ def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, 
     m.H, m.W, m.D, m.device = H, W, int(ndisp), fl.device
     m.sgm_bufs = None
     m.cbca_iters = 0          # the reference has no aggregation stage
+    m.subpixel, m.bilateral = bool(subpixel), bool(bilateral)
     timings = {}
     dl, dr = m.sgm_path(fl=fl, fr=fr, img_l=il, img_r=ir, timings=timings)
     for slot, key in ((1, "cost_volume"), (3, "sgm"), (4, "wta"), (5, "lrc"), (6, "filter")):
