@@ -24,8 +24,6 @@ import argparse
 import os
 import sys
 
-import numpy as np
-
 METHODS = ("ad", "rank", "census")
 
 
@@ -55,10 +53,8 @@ class LocalMatcher:
 
     def load_images(self, left_u8, right_u8):
         """Host u8 [H,W] arrays (or device tensors) -> resident device images."""
-        import torch
-        for dst, src in zip(self.img_u82, (left_u8, right_u8)):
-            t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, np.uint8))
-            dst.copy_(t, non_blocking=False)
+        from . import ops
+        ops.upload_u8_pair(self.img_u82, left_u8, right_u8)
 
     def match(self):
         """The left disparity map the reference script computes for this method (float32 [H,W])."""
@@ -76,11 +72,11 @@ class LocalMatcher:
     def _lr_bufs(self):
         if self.lr_bufs is None:
             import torch
-            H, W, dev = self.H, self.W, self.device
-            f32 = lambda: torch.empty((H, W), dtype=torch.float32, device=dev)   # noqa: E731
-            u8 = lambda: torch.empty((H, W), dtype=torch.uint8, device=dev)      # noqa: E731
-            self.disp_r = f32()
-            self.lr_bufs = dict(lrc=[u8(), u8()], filled=f32(), checked=f32())
+
+            from .pipeline import CheckedPath
+            self.disp_r = torch.empty((self.H, self.W), dtype=torch.float32, device=self.device)
+            self.checked = CheckedPath(self.H, self.W, self.device)
+            self.lr_bufs = self.checked.bufs
         return self.lr_bufs
 
     def match_lr(self, max_diff: float = 1.0):
@@ -92,14 +88,10 @@ class LocalMatcher:
         if self.method != "census":
             raise ValueError("match_lr needs method='census': the reference defines no right view for the "
                              "one-sided SAD windows")
-        b = self._lr_bufs()
+        self._lr_bufs()
         ops.census_transform(self.img_u82, out=self.census2)
         ops.census_wta(self.census2[0], self.census2[1], self.D, disp_l=self.disp, disp_r=self.disp_r)
-        ops.lr_consistency(self.disp, self.disp_r, max_diff, b["lrc"][0], b["lrc"][1])
-        ops.lrc_fill(self.disp, b["lrc"][0], out=b["filled"])
-        b["checked"].copy_(b["filled"])
-        ops.median5(b["filled"], b["checked"])
-        return b["checked"], self.disp_r, b["lrc"][0]
+        return self.checked.run(self.disp, self.disp_r, max_diff)
 
 
 def window_rule(W, D, k):

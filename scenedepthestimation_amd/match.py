@@ -55,6 +55,7 @@ def main(argv=None):
     from . import imageio, mc_cnn, ops
     from .parallel import init_from_env, pairs_for_rank
     from .pipeline import StereoMatcher
+    from .process_functional import add_detail_time
 
     rank, world, _ = init_from_env()
     weights = mc_cnn.load_weights(args.checkpoint, 5)
@@ -72,11 +73,8 @@ def main(argv=None):
                                     bilateral=args.bilateral)
         import time
         t0 = time.time()
-        for k, img in enumerate((_l, _r)):
-            x = normalise(img.astype(np.float32))[..., 0]
-            buf = np.zeros((H + 10, W + 10), np.float32)     # process_functional.py:13-19 (match.py:58-63)
-            buf[5:5 + H, 5:5 + W] = x
-            matcher.img_pad[k].copy_(torch.from_numpy(buf))
+        # the 5-pixel zero padding of process_functional.py:13-19 (match.py:58-63)
+        matcher.load_normalised(*(normalise(img.astype(np.float32))[..., 0] for img in (_l, _r)))
         fl, fr = matcher.features_from_padded()
         torch.cuda.synchronize()
         detail_time[0] += time.time() - t0
@@ -91,8 +89,7 @@ def main(argv=None):
             timings = {}
             dl, _ = matcher.sgm_path(timings=timings)
             disp = dl.cpu().numpy()
-            for slot, key in ((1, "cost_volume"), (3, "sgm"), (4, "wta"), (5, "lrc"), (6, "filter")):
-                detail_time[slot] += timings.get(key, 0.0)
+            add_detail_time(detail_time, timings)
         imageio.imwrite(os.path.join(args.out_path, "ld{}.png".format(i)), disp.astype("uint8") * 2)
     n = max(1, len(pairs_for_rank(args.pairs, world, rank)))
     names = ["computing features", "computing cost volume", '"*" cost aggregation', "SGM",

@@ -85,10 +85,7 @@ def lr_checked_disparity(left, right, ndisp, checkpoint, subpixel=False, bilater
                       subpixel=subpixel, bilateral=bilateral)
     if bilateral:
         m.img_u8[0].copy_(torch.from_numpy(np.ascontiguousarray(left_u8, np.uint8)))
-    for i, img in enumerate((left, right)):
-        buf = np.zeros((H + 2 * nlayers, W + 2 * nlayers), np.float32)
-        buf[nlayers:nlayers + H, nlayers:nlayers + W] = img[..., 0]
-        m.img_pad[i].copy_(torch.from_numpy(buf))
+    m.load_normalised(left[..., 0], right[..., 0])
     m.features_from_padded()
     disp, _, _ = m.lr_checked()
     return disp.cpu().numpy()

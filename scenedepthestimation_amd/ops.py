@@ -50,6 +50,26 @@ def _feat_pair(fl, fr):
     return _need(fl, "featuresl", shape=(H, W, C)), _need(fr, "featuresr", shape=(H, W, C)), H, W, C
 
 
+def _lr_volumes(shape, like, left, right, out_left, out_right):
+    """The left / right f32 volumes of a two-sided cost kernel: each side asked for is allocated on like's device
+    unless given, and validated.  Returns (left pointer, right pointer, what the op returns): the left volume,
+    (left, right) with right=True, the right one alone with left=False; a side not asked for is a null pointer."""
+    if not left and not right:
+        raise ValueError("nothing to compute")
+    ol = orr = None
+    if left:
+        if out_left is None:
+            out_left = _empty(shape, torch.float32, like)
+        ol = _need(out_left, "out_left", shape=shape)
+    if right:
+        if out_right is None:
+            out_right = _empty(shape, torch.float32, like)
+        orr = _need(out_right, "out_right", shape=shape)
+    if not left:
+        return ol, orr, out_right
+    return ol, orr, (out_left, out_right) if right else out_left
+
+
 # ----------------------------------------------------------------------------
 # cost volume / WTA (process_functional.py:48-131, 800-837)
 # ----------------------------------------------------------------------------
@@ -63,27 +83,13 @@ def cost_volume(fl, fr, ndisp: int, layout: str = "DHW", right: bool = False, in
     if invalid is None:
         invalid = -0.0 if layout == "DHW" else 1.0
     shape = (ndisp, H, W) if layout == "DHW" else (H, W, ndisp)
-    if not left and not right:
-        raise ValueError("nothing to compute")
-    ol = orr = None
-    sides = 0
-    if left:
-        if out_left is None:
-            out_left = _empty(shape, torch.float32, fl)
-        ol = _need(out_left, "out_left", shape=shape)
-        sides |= SDE_SIDE_LEFT
-    if right:
-        if layout != "HWD":
-            raise ValueError("the right volume exists in the HWD (GPU-path) layout only")
-        if out_right is None:
-            out_right = _empty(shape, torch.float32, fl)
-        orr = _need(out_right, "out_right", shape=shape)
-        sides |= SDE_SIDE_RIGHT
+    if right and layout != "HWD":
+        raise ValueError("the right volume exists in the HWD (GPU-path) layout only")
+    ol, orr, result = _lr_volumes(shape, fl, left, right, out_left, out_right)
+    sides = (SDE_SIDE_LEFT if left else 0) | (SDE_SIDE_RIGHT if right else 0)
     check(lib.sde_cost_volume(pl, pr, H, W, C, int(ndisp), lay, sides, ctypes.c_float(invalid), ol, orr,
                               _stream()), "sde_cost_volume")
-    if not left:
-        return out_right
-    return (out_left, out_right) if right else out_left
+    return result
 
 
 CV_MODES = {"exact": _lib.SDE_CV_EXACT, "certified": _lib.SDE_CV_CERTIFIED}
@@ -172,6 +178,10 @@ def cv_wta_fixups(workspace) -> int:
 
 def wta(vol, layout: str = "DHW", rule: str = "inf", out=None):
     """First-min over d: WTA1 (DHW), WTA (HWD) or the SGM WTA kernel (HWD, rule='d0')."""
+    return _wta_volume(lib.sde_wta, "sde_wta", vol, layout, rule, out)
+
+
+def _wta_volume(fn, what, vol, layout, rule, out):
     if vol.dim() != 3:
         raise ValueError("volume must be 3-D")
     if layout == "DHW":
@@ -182,7 +192,7 @@ def wta(vol, layout: str = "DHW", rule: str = "inf", out=None):
     if out is None:
         out = _empty((H, W), torch.float32, vol)
     po = _need(out, "disp", shape=(H, W))
-    check(lib.sde_wta(pv, H, W, D, LAYOUTS[layout], RULES[rule], po, _stream()), "sde_wta")
+    check(fn(pv, H, W, D, LAYOUTS[layout], RULES[rule], po, _stream()), what)
     return out
 
 
@@ -242,6 +252,15 @@ TOWER_PRECISIONS = {"fp32": _lib.SDE_TOWER_FP32, "bf16x6": _lib.SDE_TOWER_BF16X6
                     "f16x3t32": _lib.SDE_TOWER_F16X3 | _lib.SDE_TOWER_TILE32}
 
 
+# the precisions whose layers scale by f16 bound words (every f16x3 variant): the words a layer-by-layer driver
+# zeroes, fills from the image and hands from layer to layer (and row bands all-reduce) ...
+TOWER_BOUND_WORD_PRECISIONS = frozenset(p for p, f in TOWER_PRECISIONS.items() if f & _lib.SDE_TOWER_F16X3)
+# ... and those whose activations sde_tower_forward* pass between layers in the c-block-major layout (the split
+# precisions; fp32 keeps [h, w, nf])
+TOWER_CBLOCK_PRECISIONS = frozenset(p for p, f in TOWER_PRECISIONS.items()
+                                    if f & (_lib.SDE_TOWER_BF16X6 | _lib.SDE_TOWER_F16X3))
+
+
 def _split_ptrs(split, shape):
     """split = (hi int16 [..., 64], lo int16 [..., 64], norm f32 [...]) or None -> three pointers."""
     if split is None:
@@ -276,22 +295,30 @@ def tower_forward(img_pad, packed, nlayers: int, nf: int = 64, out=None, workspa
     'f16x3' (power-of-two scaled exact 2-way fp16 split, 3 partial products, fp32 accumulate).
     split: optional (hi, lo, norm) buffers the last layer's epilogue fills (certified cost volume input)."""
     Hp, Wp = img_pad.shape
+    return _tower_forward((), Hp, Wp, img_pad, packed, nlayers, nf, out, workspace, precision, split)
+
+
+def _tower_forward(lead, Hp, Wp, img_pad, packed, nlayers, nf, out, workspace, precision, split):
+    """tower_forward (lead = ()) and tower_forward_batch (lead = (N,)): the same call apart from the leading N."""
     H, W = Hp - 2 * nlayers, Wp - 2 * nlayers
     if H <= 0 or W <= 0:
         raise ValueError("padded image smaller than the tower's receptive field")
     pi = _need(img_pad, "img_pad")
     pw = _need(packed, "packed weights", shape=(tower_packed_floats(nlayers, nf),))
     if out is None:
-        out = _empty((H, W, nf), torch.float32, img_pad)
-    po = _need(out, "features", shape=(H, W, nf))
-    need = tower_workspace_bytes(H, W, nlayers, nf)
+        out = _empty(lead + (H, W, nf), torch.float32, img_pad)
+    po = _need(out, "features", shape=lead + (H, W, nf))
+    if lead:
+        fn, what, need = lib.sde_tower_forward_batch, "sde_tower_forward_batch", \
+            tower_batch_workspace_bytes(H, W, lead[0], nlayers, nf)
+    else:
+        fn, what, need = lib.sde_tower_forward, "sde_tower_forward", tower_workspace_bytes(H, W, nlayers, nf)
     if need > 0 and workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=img_pad.device)
     pws = _need(workspace, "workspace", dtype=torch.uint8) if need > 0 else None
     wsb = workspace.numel() if need > 0 else 0
-    ph, pl_, pn = _split_ptrs(split, (H, W))
-    check(lib.sde_tower_forward(pi, H, W, pw, nlayers, nf, po, pws, wsb, TOWER_PRECISIONS[precision], ph, pl_, pn,
-                                _stream()), "sde_tower_forward")
+    check(fn(pi, *lead, H, W, pw, nlayers, nf, po, pws, wsb, TOWER_PRECISIONS[precision],
+             *_split_ptrs(split, (H, W)), _stream()), what)
     return out
 
 
@@ -317,22 +344,7 @@ def tower_forward_batch(img_pad, packed, nlayers: int, nf: int = 64, out=None, w
     """img_pad: f32 [N, H+2L, W+2L] -> features f32 [N, H, W, nf], all N images per launch
     (sde_tower_forward_batch); each image's result equals tower_forward on it alone."""
     N, Hp, Wp = img_pad.shape
-    H, W = Hp - 2 * nlayers, Wp - 2 * nlayers
-    if H <= 0 or W <= 0:
-        raise ValueError("padded image smaller than the tower's receptive field")
-    pi = _need(img_pad, "img_pad")
-    pw = _need(packed, "packed weights", shape=(tower_packed_floats(nlayers, nf),))
-    if out is None:
-        out = _empty((N, H, W, nf), torch.float32, img_pad)
-    po = _need(out, "features", shape=(N, H, W, nf))
-    need = tower_batch_workspace_bytes(H, W, N, nlayers, nf)
-    if need > 0 and workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=img_pad.device)
-    pws = _need(workspace, "workspace", dtype=torch.uint8) if need > 0 else None
-    wsb = workspace.numel() if need > 0 else 0
-    check(lib.sde_tower_forward_batch(pi, N, H, W, pw, nlayers, nf, po, pws, wsb, TOWER_PRECISIONS[precision],
-                                      None, None, None, _stream()), "sde_tower_forward_batch")
-    return out
+    return _tower_forward((N,), Hp, Wp, img_pad, packed, nlayers, nf, out, workspace, precision, None)
 
 
 def absmax_batch(x, out):
@@ -446,6 +458,13 @@ def tower_layer_batch(inp, packed, nlayers: int, layer: int, out, nf: int = 64, 
     return out
 
 
+def upload_u8_pair(dst2, left, right):
+    """Host u8 [H,W] arrays (or device tensors) -> the resident pair dst2, u8 [2,H,W] on the device."""
+    for dst, src in zip(dst2, (left, right)):
+        t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, np.uint8))
+        dst.copy_(t, non_blocking=False)
+
+
 def preprocess_scratch_bytes(H: int, W: int) -> int:
     """Device scratch one image's preprocess needs (sde_preprocess_scratch_bytes)."""
     n = int(lib.sde_preprocess_scratch_bytes(int(H), int(W)))
@@ -517,38 +536,38 @@ def sgm_8path_pair(cv_l, pen_l, S_l, cv_r=None, pen_r=None, S_r=None, accumulate
     accumulate=False: S := the 8-path sum from zero (S need not be zeroed).
     zero_du_penalties=True: the penalties come from sgm_penalties (channels 0/1 zero) and
     the costs are finite -- direction DU is folded into the UD pass (same values)."""
-    H, W, D = cv_l.shape
-    args = [_need(cv_l, "cost volume"), _need(pen_l, "penalties", shape=(H, W, 16)), _need(S_l, "S", shape=(H, W, D))]
-    if cv_r is None:
-        args += [None, None, None]
+    _sgm_pair(lib.sde_sgm_8path_pair, "sde_sgm_8path_pair", (cv_l, pen_l, S_l), (cv_r, pen_r, S_r), accumulate,
+              zero_du_penalties)
+    return S_l, S_r
+
+
+def _sgm_pair(fn, what, left, right, accumulate, zero_du_penalties):
+    """One launch sequence over both sides.  left / right: (cost volume, penalties, S[, disp]); the right side
+    is null pointers when its volume is None (the left side alone)."""
+    H, W, D = left[0].shape
+    shapes = (None, (H, W, 16), (H, W, D), (H, W))
+    names = ("cost volume", "penalties", "S", "disp")
+    args = [_need(t, n, shape=sh) for t, n, sh in zip(left, names, shapes)]
+    if right[0] is None:
+        args += [None] * len(right)
     else:
-        args += [_need(cv_r, "cost volume", shape=(H, W, D)), _need(pen_r, "penalties", shape=(H, W, 16)),
-                 _need(S_r, "S", shape=(H, W, D))]
+        args += [_need(t, n, shape=sh) for t, n, sh in zip(right, names, ((H, W, D),) + shapes[1:])]
     flags = (_lib.SDE_SGM_ACCUMULATE if accumulate else 0) | \
         (_lib.SDE_SGM_ZERO_DU_PENALTIES if zero_du_penalties else 0)
-    check(lib.sde_sgm_8path_pair(*args, H, W, D, flags, _stream()), "sde_sgm_8path_pair")
-    return S_l, S_r
+    check(fn(*args, H, W, D, flags, _stream()), what)
 
 
 def sgm_8path_wta_pair(cv_l, pen_l, S_l, disp_l=None, cv_r=None, pen_r=None, S_r=None, disp_r=None,
                        accumulate=False, zero_du_penalties=False):
     """sgm_8path_pair + WTA (rule "d0") fused into the last direction (sde_sgm_8path_wta_pair):
     returns the disparity maps; S is left holding the first seven directions' sum."""
-    H, W, D = cv_l.shape
+    H, W, _ = cv_l.shape
     if disp_l is None:
         disp_l = _empty((H, W), torch.float32, cv_l)
-    args = [_need(cv_l, "cost volume"), _need(pen_l, "penalties", shape=(H, W, 16)), _need(S_l, "S", shape=(H, W, D)),
-            _need(disp_l, "disp", shape=(H, W))]
-    if cv_r is None:
-        args += [None, None, None, None]
-    else:
-        if disp_r is None:
-            disp_r = _empty((H, W), torch.float32, cv_l)
-        args += [_need(cv_r, "cost volume", shape=(H, W, D)), _need(pen_r, "penalties", shape=(H, W, 16)),
-                 _need(S_r, "S", shape=(H, W, D)), _need(disp_r, "disp", shape=(H, W))]
-    flags = (_lib.SDE_SGM_ACCUMULATE if accumulate else 0) | \
-        (_lib.SDE_SGM_ZERO_DU_PENALTIES if zero_du_penalties else 0)
-    check(lib.sde_sgm_8path_wta_pair(*args, H, W, D, flags, _stream()), "sde_sgm_8path_wta_pair")
+    if cv_r is not None and disp_r is None:
+        disp_r = _empty((H, W), torch.float32, cv_l)
+    _sgm_pair(lib.sde_sgm_8path_wta_pair, "sde_sgm_8path_wta_pair", (cv_l, pen_l, S_l, disp_l),
+              (cv_r, pen_r, S_r, disp_r), accumulate, zero_du_penalties)
     return disp_l, disp_r
 
 
@@ -700,18 +719,7 @@ def wta_subpixel(vol, layout: str = "DHW", rule: str = "inf", out=None):
     """wta(vol, layout, rule) followed by the parabola step on the winner's two neighbours in the stored volume
     (sde_wta_subpixel): a winner at d = 0 or D - 1, a non-finite neighbour, a parabola that is not convex and a
     pixel without a winner (-1) keep the integer."""
-    if vol.dim() != 3:
-        raise ValueError("volume must be 3-D")
-    if layout == "DHW":
-        D, H, W = vol.shape
-    else:
-        H, W, D = vol.shape
-    pv = _need(vol, "volume")
-    if out is None:
-        out = _empty((H, W), torch.float32, vol)
-    po = _need(out, "disp", shape=(H, W))
-    check(lib.sde_wta_subpixel(pv, H, W, D, LAYOUTS[layout], RULES[rule], po, _stream()), "sde_wta_subpixel")
-    return out
+    return _wta_volume(lib.sde_wta_subpixel, "sde_wta_subpixel", vol, layout, rule, out)
 
 
 def cv_subpixel(fl, fr, d0: int, d1: int, disp, side: str = "left", out=None):
@@ -752,33 +760,28 @@ LOCAL_INVALID = _lib.SDE_LOCAL_INVALID
 LOCAL_MAX_RADIUS = _lib.SDE_LOCAL_MAX_RADIUS
 
 
-def _images(imgs, name="images"):
-    """u8 [H,W] or [N,H,W] -> (pointer, N, H, W)."""
+def _transform(fn, what, imgs, out, dtype, name):
+    """A per-pixel transform of u8 [H,W] or [N,H,W] images into `dtype` words of the same shape, all images per
+    launch."""
     if not isinstance(imgs, torch.Tensor) or imgs.dim() not in (2, 3):
-        raise ValueError(f"{name} must be a uint8 [H,W] or [N,H,W] tensor")
-    p = _need(imgs, name, dtype=torch.uint8)
+        raise ValueError("images must be a uint8 [H,W] or [N,H,W] tensor")
+    p = _need(imgs, "images", dtype=torch.uint8)
     H, W = imgs.shape[-2:]
-    return p, (imgs.shape[0] if imgs.dim() == 3 else 1), H, W
+    if out is None:
+        out = _empty(tuple(imgs.shape), dtype, imgs)
+    check(fn(p, imgs.shape[0] if imgs.dim() == 3 else 1, H, W, _need(out, name, dtype=dtype, shape=tuple(imgs.shape)),
+             _stream()), what)
+    return out
 
 
 def census_transform(imgs, out=None):
     """u8 [H,W] or [N,H,W] -> the 19-bit census words as int32 of the same shape (sde_census_transform)."""
-    p, N, H, W = _images(imgs)
-    if out is None:
-        out = _empty(tuple(imgs.shape), torch.int32, imgs)
-    check(lib.sde_census_transform(p, N, H, W, _need(out, "census", dtype=torch.int32, shape=tuple(imgs.shape)),
-                                   _stream()), "sde_census_transform")
-    return out
+    return _transform(lib.sde_census_transform, "sde_census_transform", imgs, out, torch.int32, "census")
 
 
 def rank_transform(imgs, out=None):
     """u8 [H,W] or [N,H,W] -> the 7x7 rank (1..49) as uint8 of the same shape (sde_rank_transform)."""
-    p, N, H, W = _images(imgs)
-    if out is None:
-        out = _empty(tuple(imgs.shape), torch.uint8, imgs)
-    check(lib.sde_rank_transform(p, N, H, W, _need(out, "rank", dtype=torch.uint8, shape=tuple(imgs.shape)),
-                                 _stream()), "sde_rank_transform")
-    return out
+    return _transform(lib.sde_rank_transform, "sde_rank_transform", imgs, out, torch.uint8, "rank")
 
 
 def _census_pair(census_l, census_r):
@@ -794,23 +797,10 @@ def census_cost(census_l, census_r, ndisp: int, invalid: float = LOCAL_INVALID, 
     """The Hamming volumes f32 [H,W,D] (sde_census_cost): the left one, (left, right) with right=True, the
     right one alone with left=False."""
     pl, pr, H, W = _census_pair(census_l, census_r)
-    if not left and not right:
-        raise ValueError("nothing to compute")
-    shape = (H, W, int(ndisp))
-    ol = orr = None
-    if left:
-        if out_left is None:
-            out_left = _empty(shape, torch.float32, census_l)
-        ol = _need(out_left, "out_left", shape=shape)
-    if right:
-        if out_right is None:
-            out_right = _empty(shape, torch.float32, census_l)
-        orr = _need(out_right, "out_right", shape=shape)
+    ol, orr, result = _lr_volumes((H, W, int(ndisp)), census_l, left, right, out_left, out_right)
     check(lib.sde_census_cost(pl, pr, H, W, int(ndisp), ctypes.c_float(invalid), ol, orr, _stream()),
           "sde_census_cost")
-    if not left:
-        return out_right
-    return (out_left, out_right) if right else out_left
+    return result
 
 
 def census_wta(census_l, census_r, ndisp: int, left: bool = True, right: bool = True, want_min: bool = False,

@@ -127,6 +127,19 @@ def allreduce_max_(words: torch.Tensor, group=None):
     return words
 
 
+def sync_bound_words(steps, precision, nlayers, device, group=None):
+    """Drive a row band's tower_steps to the end, all-reducing (MAX) the f16 bound words at every yield, so each
+    rank scales every layer by the whole image's bound.  steps=None is an empty band: it runs no tower but joins
+    the same nlayers - 1 all-reduces with zero words -- a rank that joined fewer would deadlock the group."""
+    from . import ops
+    synced = precision in ops.TOWER_BOUND_WORD_PRECISIONS
+    if steps is None:
+        steps = [(0, torch.zeros((2, 64), dtype=torch.float32, device=device))] * (nlayers - 1) if synced else []
+    for _stage, words in steps:
+        if synced:
+            allreduce_max_(words, group)
+
+
 class DisparityShardedMatcher:
     """Config 5: features from row bands + all-gather, disparity-sharded fused CV/WTA + all-gather merge.
 
@@ -173,17 +186,10 @@ class DisparityShardedMatcher:
         from . import ops
         m, L = self.m, self.m.nlayers
         ops.preprocess_u8_batch(m.img_u82, L, out=m.img_pad2, stats=m.stats2)
-        if self.band_pad is not None:
-            for _stage, words in self.band_steps():
-                if m.tower_precision in ("f16x3", "f16x3w", "f16x3m32", "f16x3t32"):
-                    allreduce_max_(words, self.group)
-            if self.band_out is not self.band:
-                self.band[:, :self.r1 - self.r0].copy_(self.band_out)
-        elif m.tower_precision in ("f16x3", "f16x3w", "f16x3m32", "f16x3t32"):
-            # an empty band still joins every bound all-reduce (same count as the other ranks)
-            words = torch.zeros((2, 64), dtype=torch.float32, device=m.device)
-            for _ in range(L - 1):
-                allreduce_max_(words, self.group)
+        sync_bound_words(self.band_steps() if self.band_pad is not None else None, m.tower_precision, L, m.device,
+                         self.group)
+        if self.band_pad is not None and self.band_out is not self.band:
+            self.band[:, :self.r1 - self.r0].copy_(self.band_out)
         all_gather_into(self.full, self.band, self.group)
         full = self.full.view(self.world, 2, self.rpb, self.W, m.nf)
         for i in range(2):
@@ -252,10 +258,8 @@ class FullImages:
         self.stats2 = torch.empty((2 * ops.preprocess_scratch_bytes(H, W),), dtype=torch.uint8, device=self.device)
 
     def load_images(self, left_u8, right_u8):
-        import numpy as np
-        for dst, src in zip(self.img_u82, (left_u8, right_u8)):
-            t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, np.uint8))
-            dst.copy_(t, non_blocking=False)
+        from . import ops
+        ops.upload_u8_pair(self.img_u82, left_u8, right_u8)
 
 
 class RowBandMatcher:
@@ -291,17 +295,13 @@ class RowBandMatcher:
         from .pipeline import tower_steps
         f, L = self.full, self.nlayers
         ops.preprocess_u8_batch(f.img_u82, L, out=f.img_pad2, stats=f.stats2)
+        steps = None
         if self.band is not None:
             b = self.band
             b.img_pad2.copy_(f.img_pad2[:, self.r0:self.r1 + 2 * L])
-            for _stage, words in tower_steps(b.img_pad2, b.packed, L, b.feat2, b.ws, b.tower_precision, b.nf):
-                if b.tower_precision in ("f16x3", "f16x3w", "f16x3m32", "f16x3t32"):
-                    allreduce_max_(words, self.group)
+            steps = tower_steps(b.img_pad2, b.packed, L, b.feat2, b.ws, b.tower_precision, b.nf)
             b.split_valid = False
-        elif f.tower_precision in ("f16x3", "f16x3w", "f16x3m32", "f16x3t32"):
-            words = torch.zeros((2, 64), dtype=torch.float32, device=f.device)
-            for _ in range(L - 1):
-                allreduce_max_(words, self.group)
+        sync_bound_words(steps, f.tower_precision, L, f.device, self.group)
 
     def match(self):
         self.features()

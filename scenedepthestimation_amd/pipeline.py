@@ -28,7 +28,7 @@ from . import mc_cnn, ops
 
 AMAX_WORDS = ops.AMAX_ROW_WORDS   # f16x3 bound words per image in the tower workspace (TOWER_AMAX_BYTES / 4)
 SPLIT_MAX_PIX = 1 << 24   # split activations: fewer input pixels per plane than this (tower.hip SPLIT_MAX_PIX)
-# Placement draws of the four SGM volumes (StereoMatcher._place_sgm_volumes): volumes of [MIN, MAX] voxels are
+# Placement draws of the four SGM volumes (SgmPath._place_volumes): volumes of [MIN, MAX] voxels are
 # placed by up to this many allocate-and-time draws (larger ones would hold three 4-volume sets of > 6 GB each).
 SGM_PLACEMENT_TRIALS = 16   # round 6: 8 draws missed the fast mode on some boxes (7 slow draws seen in a row)
 SGM_PLACEMENT_MIN_VOXELS = 1 << 26
@@ -56,12 +56,12 @@ def tower_steps(img_pad, packed, nlayers: int, out, ws, precision: str = "f16x3"
     # between layers: what sde_tower_forward_batch passes -- split activations on the f16x3 tower when
     # built with them (ops.TOWER_SPLIT_ACT; <= 32 layers, < 2^24 pixels), else c-block-major fp32
     sp = ops.TOWER_SPLIT_ACT and precision == "f16x3" and 2 < L <= ops.SCALE_WORD and h2 * w2 < SPLIT_MAX_PIX
-    cbl = not sp and precision in ("bf16x6", "f16x3", "f16x3w", "f16x3m32", "f16x3t32")
+    cbl = not sp and precision in ops.TOWER_CBLOCK_PRECISIONS
     act = h2 * w2 * nf if L > 2 else 0
     wsf = ws[: 2 * N * act * 4 + N * AMAX_WORDS * 4].view(torch.float32)
     bufs = [wsf[: N * act], wsf[N * act: 2 * N * act]]
     words = wsf[2 * N * act:].view(N, AMAX_WORDS)
-    f16 = precision in ("f16x3", "f16x3w", "f16x3m32", "f16x3t32")
+    f16 = precision in ops.TOWER_BOUND_WORD_PRECISIONS
     if f16:
         words.zero_()
         ops.absmax_batch(img_pad, words)
@@ -114,7 +114,6 @@ class StereoMatcher:
         self.cbca_iters, self.cbca_L1, self.cbca_tau = int(cbca_iters), int(cbca_L1), float(cbca_tau)
         self.nlayers, self.nf = int(nlayers), int(nf)
         self.sgm_placement_trials = int(sgm_placement_trials)
-        self.sgm_placement_ms = None     # the SGM pair time of each placement draw (_place_sgm_volumes)
         if tower_precision not in ops.TOWER_PRECISIONS:
             raise ValueError(f"tower_precision must be one of {sorted(ops.TOWER_PRECISIONS)}")
         self.tower_precision = tower_precision
@@ -154,9 +153,21 @@ class StereoMatcher:
             if (emit_split and cv_mode == "certified" and nlayers >= 2) else None
         self.split_valid = False
         self.lr_bufs = None    # the right view and the checked path's maps, allocated on first use (_lr_bufs)
-        self.sgm_bufs = None
+        # the GPU path of disparity_compute_by_gpu; its aggregation stage borrows the tower's input buffers for
+        # the z-normalised images
+        self.sgm = SgmPath(H, W, self.D, dev, self.cbca_iters, self.cbca_L1, self.cbca_tau, self.subpixel,
+                           self.bilateral, self.sgm_placement_trials, scratch=(self.img_pad, self.stats, L))
         if sgm:
-            self._alloc_sgm()
+            self.sgm.alloc()
+
+    @property
+    def sgm_bufs(self):
+        """The SGM path's buffers (SgmPath.alloc), None until the path has run or sgm=True asked for them."""
+        return self.sgm.bufs
+
+    @property
+    def sgm_placement_ms(self):
+        return self.sgm.placement_ms
 
     @property
     def ws(self):
@@ -171,9 +182,16 @@ class StereoMatcher:
     # -- stages ----------------------------------------------------------------
     def load_images(self, left_u8, right_u8):
         """Host u8 [H,W] arrays (or device tensors) -> resident device images."""
-        for dst, src in zip(self.img_u8, (left_u8, right_u8)):
-            t = src if isinstance(src, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src, np.uint8))
-            dst.copy_(t, non_blocking=False)
+        ops.upload_u8_pair(self.img_u82, left_u8, right_u8)
+
+    def load_normalised(self, left, right):
+        """Two normalised host images f32 [H,W] -> the tower's zero-padded input (process_functional.py:13-19),
+        for features_from_padded()."""
+        H, W, L = self.H, self.W, self.nlayers
+        for dst, img in zip(self.img_pad, (left, right)):
+            buf = np.zeros((H + 2 * L, W + 2 * L), np.float32)
+            buf[L:L + H, L:L + W] = img
+            dst.copy_(torch.from_numpy(buf))
 
     def features(self, on_launch=None):
         """Preprocess + tower for both images (compute_feature, process_functional.py:11-45).
@@ -233,14 +251,12 @@ class StereoMatcher:
         that only runs match() never holds them."""
         if self.lr_bufs is None:
             H, W, dev = self.H, self.W, self.device
-            f32 = lambda: torch.empty((H, W), dtype=torch.float32, device=dev)   # noqa: E731
-            u8 = lambda: torch.empty((H, W), dtype=torch.uint8, device=dev)      # noqa: E731
-            self.disp_r, self.min_cost_r = f32(), f32()
+            self.disp_r = torch.empty((H, W), dtype=torch.float32, device=dev)
+            self.min_cost_r = torch.empty((H, W), dtype=torch.float32, device=dev)
             self.argmin_r = torch.empty((H, W), dtype=torch.int32, device=dev)
             self.cv_ws_r = torch.empty(ops.cv_wta_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
-            self.lr_bufs = dict(lrc=[u8(), u8()], filled=f32(), checked=f32())
-            if self.bilateral:
-                self.lr_bufs["smoothed"] = f32()
+            self.checked = CheckedPath(H, W, dev, self.bilateral)
+            self.lr_bufs = self.checked.bufs
         return self.lr_bufs
 
     def cost_wta_right(self, want=("disp",)):
@@ -265,22 +281,13 @@ class StereoMatcher:
         image (the reference's dead call, :1260, would filter the LRC-filled map and overwrite the median's
         result: a documented divergence)."""
         self._need_whole_range()
-        b = self._lr_bufs()
+        self._lr_bufs()
         self.cost_wta()
         self.cost_wta_right()
         if self.subpixel:
             ops.cv_subpixel(self.feat[0], self.feat[1], self.d0, self.d1, self.disp, "left", out=self.disp)
             ops.cv_subpixel(self.feat[0], self.feat[1], self.d0, self.d1, self.disp_r, "right", out=self.disp_r)
-        ops.lr_consistency(self.disp, self.disp_r, max_diff, b["lrc"][0], b["lrc"][1])
-        ops.lrc_fill(self.disp, b["lrc"][0], out=b["filled"])
-        # the 5x5 median of the filled map into the interior of a copy of it: the 2-pixel border keeps the
-        # filled values
-        b["checked"].copy_(b["filled"])
-        ops.median5(b["filled"], b["checked"])
-        if self.bilateral:
-            ops.bilateral9(self.img_u8[0], b["checked"], out=b["smoothed"])
-            return b["smoothed"], self.disp_r, b["lrc"][0]
-        return b["checked"], self.disp_r, b["lrc"][0]
+        return self.checked.run(self.disp, self.disp_r, max_diff, self.img_u8[0])
 
     def match_lr(self, max_diff: float = 1.0):
         """The hot path with the reference's post-processing (is_error_match / LRC / median,
@@ -293,7 +300,67 @@ class StereoMatcher:
         return self.lr_checked(max_diff)
 
     # -- GPU path of disparity_compute_by_gpu ---------------------------------
-    def _place_sgm_volumes(self, pen, disp):
+    def cbca(self, cv_l, cv_r, img_l, img_r):
+        """SgmPath.cbca on this matcher's path (arms from the z-normalised images, in the tower's input buffers)."""
+        return self.sgm.cbca(cv_l, cv_r, img_l, img_r)
+
+    def sgm_path(self, fl=None, fr=None, img_l=None, img_r=None, timings=None, post=True):
+        """SgmPath.run on this matcher's features and resident u8 images unless others are given."""
+        return self.sgm.run(self.feat[0] if fl is None else fl, self.feat[1] if fr is None else fr,
+                            self.img_u8[0] if img_l is None else img_l, self.img_u8[1] if img_r is None else img_r,
+                            timings=timings, post=post)
+
+
+class CheckedPath:
+    """The reference's post-processing of two views' raw maps (is_error_match / LRC / median,
+    process_functional.py:977-1088, :840-879) and the maps it writes: the wrap-free left-right check, LRC fill of
+    the left map, 5x5 median and, with bilateral=True, the 9x9 bilateral filter of the median's output.  Shared by
+    StereoMatcher.lr_checked and LocalMatcher.match_lr."""
+
+    def __init__(self, H, W, device, bilateral: bool = False):
+        f32 = lambda: torch.empty((H, W), dtype=torch.float32, device=device)   # noqa: E731
+        u8 = lambda: torch.empty((H, W), dtype=torch.uint8, device=device)      # noqa: E731
+        self.bufs = dict(lrc=[u8(), u8()], filled=f32(), checked=f32())
+        if bilateral:
+            self.bufs["smoothed"] = f32()
+
+    def run(self, disp_l, disp_r, max_diff: float = 1.0, img_l=None):
+        """-> (disp_l_checked, disp_r, lrc_l).  img_l: the left u8 image (the bilateral filter's intensities)."""
+        b = self.bufs
+        ops.lr_consistency(disp_l, disp_r, max_diff, b["lrc"][0], b["lrc"][1])
+        ops.lrc_fill(disp_l, b["lrc"][0], out=b["filled"])
+        # the 5x5 median of the filled map into the interior of a copy of it: the 2-pixel border keeps the
+        # filled values
+        b["checked"].copy_(b["filled"])
+        ops.median5(b["filled"], b["checked"])
+        if "smoothed" in b:
+            ops.bilateral9(img_l, b["checked"], out=b["smoothed"])
+            return b["smoothed"], disp_r, b["lrc"][0]
+        return b["checked"], disp_r, b["lrc"][0]
+
+
+class SgmPath:
+    """The GPU path of disparity_compute_by_gpu (process_functional.py:1093-1267) on device tensors, for one
+    (H, W, D) problem: it owns the path's buffers (`bufs`, allocated on first use) and takes the features and the
+    u8 images as arguments, so it runs with or without a StereoMatcher around it.
+
+    cbca_iters > 0 puts cross-based aggregation (build-defined; 0 = the reference's path) before SGM; its arms come
+    from the z-normalised images, which need scratch = (img_pad, stats, pad): two f32 [H+2p, W+2p] buffers and
+    two ops.preprocess_scratch_bytes(H, W) scratch tensors (StereoMatcher lends the tower's input buffers).
+    subpixel / bilateral: the two stages the reference carries switched off (see run)."""
+
+    def __init__(self, height: int, width: int, ndisp: int, device, cbca_iters: int = 0, cbca_L1: int = 14,
+                 cbca_tau: float = 0.02, subpixel: bool = False, bilateral: bool = False,
+                 placement_trials: int = SGM_PLACEMENT_TRIALS, scratch=None):
+        self.H, self.W, self.D, self.device = int(height), int(width), int(ndisp), torch.device(device)
+        self.cbca_iters, self.cbca_L1, self.cbca_tau = int(cbca_iters), int(cbca_L1), float(cbca_tau)
+        self.subpixel, self.bilateral = bool(subpixel), bool(bilateral)
+        self.placement_trials = int(placement_trials)
+        self.placement_ms = None     # the SGM pair time of each placement draw (_place_volumes)
+        self.scratch = scratch
+        self.bufs = None
+
+    def _place_volumes(self, pen, disp):
         """The four [H,W,D] volumes of the GPU path (cost L/R, SGM S L/R), placed by allocate-and-time draws.
 
         The 7-launch SGM pair moves the same bytes through any four volumes, yet on MI355X it runs in one of two
@@ -308,7 +375,7 @@ class StereoMatcher:
 
         def new_set():
             return [torch.empty((H, W, D), dtype=torch.float32, device=dev) for _ in range(4)]
-        trials = self.sgm_placement_trials if SGM_PLACEMENT_MIN_VOXELS <= H * W * D <= SGM_PLACEMENT_MAX_VOXELS else 1
+        trials = self.placement_trials if SGM_PLACEMENT_MIN_VOXELS <= H * W * D <= SGM_PLACEMENT_MAX_VOXELS else 1
         if trials <= 1:
             return new_set()
         for p in pen:
@@ -343,30 +410,34 @@ class StereoMatcher:
                 break
         del prev, cur
         torch.cuda.empty_cache()
-        self.sgm_placement_ms = times
+        self.placement_ms = times
         return best
 
-    def _alloc_sgm(self):
-        H, W, D, dev = self.H, self.W, self.D, self.device
-        pen = [torch.empty((H, W, 16), dtype=torch.float32, device=dev) for _ in range(2)]
-        disp = [torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(2)]
-        cvl, cvr, sl, sr = self._place_sgm_volumes(pen, disp)
-        # the right volume starts as the GPU path's invalid fill (1.0): with aggregation on, the cost
-        # volume sweep writes the left volume only and sde_cbca_lr the right one's valid voxels, so its
-        # invalid voxels (x + d >= W) keep this fill -- the value the two-volume sweep writes there
-        cvr.fill_(1.0)
-        self.sgm_bufs = dict(
-            cv=[cvl, cvr],
-            pen=pen,
-            S=[sl, sr],
-            disp=disp,
-            lrc=[torch.empty((H, W), dtype=torch.uint8, device=dev) for _ in range(2)],
-            disp_a=torch.empty((H, W), dtype=torch.float32, device=dev),
-            disp_b=torch.empty((H, W), dtype=torch.float32, device=dev),
-        )
-        if self.cbca_iters > 0:
-            self.sgm_bufs["arms"] = [torch.empty((H, W), dtype=torch.int32, device=dev) for _ in range(2)]
-            self.sgm_bufs["cbca_ws"] = torch.empty((ops.cbca_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
+    def alloc(self, arms: bool = False):
+        """The path's buffers, allocated on first use; the aggregation's arms and workspace with cbca_iters > 0 or
+        when asked for (a cbca() call on a path whose run() does not aggregate)."""
+        H, W, dev = self.H, self.W, self.device
+        if self.bufs is None:
+            pen = [torch.empty((H, W, 16), dtype=torch.float32, device=dev) for _ in range(2)]
+            disp = [torch.empty((H, W), dtype=torch.float32, device=dev) for _ in range(2)]
+            cvl, cvr, sl, sr = self._place_volumes(pen, disp)
+            # the right volume starts as the GPU path's invalid fill (1.0): with aggregation on, the cost
+            # volume sweep writes the left volume only and sde_cbca_lr the right one's valid voxels, so its
+            # invalid voxels (x + d >= W) keep this fill -- the value the two-volume sweep writes there
+            cvr.fill_(1.0)
+            self.bufs = dict(
+                cv=[cvl, cvr],
+                pen=pen,
+                S=[sl, sr],
+                disp=disp,
+                lrc=[torch.empty((H, W), dtype=torch.uint8, device=dev) for _ in range(2)],
+                disp_a=torch.empty((H, W), dtype=torch.float32, device=dev),
+                disp_b=torch.empty((H, W), dtype=torch.float32, device=dev),
+            )
+        if (arms or self.cbca_iters > 0) and "arms" not in self.bufs:
+            self.bufs["arms"] = [torch.empty((H, W), dtype=torch.int32, device=dev) for _ in range(2)]
+            self.bufs["cbca_ws"] = torch.empty((ops.cbca_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
+        return self.bufs
 
     def cbca(self, cv_l, cv_r, img_l, img_r):
         """Cross-based aggregation (build-defined) of the left [H,W,D] volume in
@@ -377,14 +448,13 @@ class StereoMatcher:
         cv_l and their input is never read -- correct only because the GPU path's right volume IS the
         left one's shear (one sweep computes each voxel once, sec. 3.1).  Its invalid voxels are kept.
         For two independent volumes use ops.cbca_pair."""
-        if self.sgm_bufs is None or "arms" not in self.sgm_bufs:
-            saved, self.cbca_iters = self.cbca_iters, max(self.cbca_iters, 1)
-            self._alloc_sgm()
-            self.cbca_iters = saved
-        b, P, H, W = self.sgm_bufs, self.nlayers, self.H, self.W
+        if self.scratch is None:
+            raise ValueError("aggregation needs scratch=(img_pad, stats, pad) for the z-normalised images")
+        b, H, W = self.alloc(arms=True), self.H, self.W
+        img_pad, stats, P = self.scratch
         for k, img in enumerate((img_l, img_r)):
-            ops.preprocess_u8(img, P, out=self.img_pad[k], stats=self.stats[k])
-            ops.cbca_arms(self.img_pad[k][P:P + H, P:P + W], self.cbca_L1, self.cbca_tau, out=b["arms"][k])
+            ops.preprocess_u8(img, P, out=img_pad[k], stats=stats[k])
+            ops.cbca_arms(img_pad[k][P:P + H, P:P + W], self.cbca_L1, self.cbca_tau, out=b["arms"][k])
         # the right volume is the left one's shear (valid voxels), so its aggregation is the shear of the
         # left one's (definition v2): one volume aggregated, then one shear pass writes cv_r's valid voxels
         # (their input is not read; its invalid voxels are kept).  The SGM S buffer (written later,
@@ -393,20 +463,14 @@ class StereoMatcher:
                     workspace=b["cbca_ws"])
         return cv_l, cv_r
 
-    def sgm_path(self, fl=None, fr=None, img_l=None, img_r=None, timings=None, post=True):
+    def run(self, fl, fr, img_l, img_r, timings=None, post=True):
         """process_functional.py:1093-1267 on device tensors; returns (disp_l, disp_r).  subpixel=True: the
         unfused SGM pair followed by ops.wta_subpixel per side instead of the fused last direction;
         bilateral=True: the 9x9 bilateral filter of each median-filtered map with its own image.
 
         timings: optional dict receiving per-stage seconds (synchronised)."""
         import time
-        if self.sgm_bufs is None:
-            self._alloc_sgm()
-        b = self.sgm_bufs
-        fl = self.feat[0] if fl is None else fl
-        fr = self.feat[1] if fr is None else fr
-        img_l = self.img_u8[0] if img_l is None else img_l
-        img_r = self.img_u8[1] if img_r is None else img_r
+        b = self.alloc()
 
         def mark(name, t0):
             if timings is not None:

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import mc_cnn, ops
-from .pipeline import StereoMatcher
+from .pipeline import SgmPath, StereoMatcher
 
 __all__ = ["compute_feature", "compute_cost_volume", "WTA", "WTA1", "disparity_compute_by_gpu"]
 
@@ -59,11 +59,7 @@ def compute_feature(left_image, right_image, patch_height, patch_width, num_of_f
     H, W = li.shape
     weights = mc_cnn.load_weights(checkpoint, nlayers)
     m = StereoMatcher(H, W, 1, weights=weights, nlayers=nlayers, nf=num_of_feature_maps, device=_device())
-    pad = (patch_height - 1) // 2                       # zero padding, process_functional.py:13-19
-    for i, img in enumerate((li, ri)):
-        buf = np.zeros((H + 2 * pad, W + 2 * pad), np.float32)
-        buf[pad:pad + H, pad:pad + W] = img
-        m.img_pad[i].copy_(torch.from_numpy(buf))
+    m.load_normalised(li, ri)                           # zero padding of (patch - 1) / 2 = nlayers pixels
     fl, fr = m.features_from_padded()
     return fl.cpu().numpy(), fr.cpu().numpy()
 
@@ -92,6 +88,17 @@ def WTA1(left_cost_volume):
     return _checked(ops.wta(_to_dev(left_cost_volume), layout="DHW", rule="inf"))
 
 
+# detail_time slot of every stage SgmPath.run times (match.py:71-75; [0] features, [2] the "*" aggregation)
+DETAIL_TIME_SLOTS = {"cost_volume": 1, "sgm": 3, "wta": 4, "lrc": 5, "filter": 6}
+
+
+def add_detail_time(detail_time, timings):
+    """Add SgmPath.run's per-stage seconds to the reference's detail_time array, in place."""
+    for key, slot in DETAIL_TIME_SLOTS.items():
+        detail_time[slot] += timings.get(key, 0.0)
+    return detail_time
+
+
 def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, ndisp=128, subpixel=False,
                              bilateral=False):
     """GPU path (process_functional.py:1093-1267): cost volume [H,W,D] (L, R; 1.0 fill),
@@ -110,14 +117,9 @@ def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, 
     ir = _to_dev(imager, np.uint8)
     if fl.shape[:2] != (H, W):
         raise ValueError("features and images differ in size")
-    m = StereoMatcher.__new__(StereoMatcher)
-    m.H, m.W, m.D, m.device = H, W, int(ndisp), fl.device
-    m.sgm_bufs = None
-    m.cbca_iters = 0          # the reference has no aggregation stage
-    m.subpixel, m.bilateral = bool(subpixel), bool(bilateral)
+    # cbca_iters = 0: the reference has no aggregation stage
+    path = SgmPath(H, W, int(ndisp), fl.device, cbca_iters=0, subpixel=subpixel, bilateral=bilateral)
     timings = {}
-    dl, dr = m.sgm_path(fl=fl, fr=fr, img_l=il, img_r=ir, timings=timings)
-    for slot, key in ((1, "cost_volume"), (3, "sgm"), (4, "wta"), (5, "lrc"), (6, "filter")):
-        detail_time[slot] += timings.get(key, 0.0)
-    return dl.cpu().numpy(), dr.cpu().numpy(), detail_time
+    dl, dr = path.run(fl, fr, il, ir, timings=timings)
+    return dl.cpu().numpy(), dr.cpu().numpy(), add_detail_time(detail_time, timings)
 
