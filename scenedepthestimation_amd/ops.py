@@ -331,7 +331,8 @@ def absmax(x, out):
 
 def set_persistent_grid(cus: int = 0):
     """Cap the persistent tower kernels' grid at `cus` workgroups (0: one per device CU), for a tower that
-    shares the device with work on CU-masked streams (sde_set_persistent_grid)."""
+    shares the device with work on CU-masked streams (sde_set_persistent_grid).  Results do not depend on it
+    (tests/test_gpu_tower_epilogue.py, test_capped_grid_*: features and bound words under 1-3 workgroups)."""
     check(lib.sde_set_persistent_grid(int(cus)), "sde_set_persistent_grid")
 
 
