@@ -11,6 +11,8 @@ Submodules
   match_single, match  the reference's CLI entry points
   training, train    Trainer / TripletSampler / PatchFileDataset and the reference's training CLI
   pfm                PFM reader / writer of the training patch files
+  rectify            StereoCalibration, stereo_rectify, Rectifier: raw calibrated pair -> rectified pair on the
+                     GPU, disparity -> depth / XYZ (include/sde_geom.h)
 """
 __version__ = "0.1.0"
 

@@ -50,7 +50,7 @@ def sources():
 
 def _headers_mtime():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hs.append(os.path.join(INCLUDE, "sde.h"))
+    hs += [os.path.join(INCLUDE, "sde.h"), os.path.join(INCLUDE, "sde_geom.h")]
     return max(os.path.getmtime(h) for h in hs)
 
 

@@ -1,11 +1,11 @@
-"""ctypes binding of libsde.so (the C ABI declared in include/sde.h).
+"""ctypes binding of libsde.so (the C ABI declared in include/sde.h, and the geometry stage's in include/sde_geom.h).
 
 torch is imported first on purpose: its bundled HIP runtime (SONAME
 libamdhip64.so.7) is then the one libsde.so binds to, so device pointers and
 streams handed over from torch are valid in our launches.
 
 There is no fallback: if the library is missing or does not export a symbol of
-include/sde.h, importing this module raises.
+either header, importing this module raises.
 """
 from __future__ import annotations
 
@@ -17,13 +17,15 @@ import torch  # noqa: F401  (load torch's HIP runtime before libsde.so)
 
 from ._build import INCLUDE, LIB
 
-HEADER = os.path.join(INCLUDE, "sde.h")
+# function prefix -> the header that declares it; constants carry the prefix in capitals (SDE_*, SDG_*)
+HEADER_NAMES = {"sde": "sde.h", "sdg": "sde_geom.h"}
+HEADER = os.path.join(INCLUDE, HEADER_NAMES["sde"])
+GEOM_HEADER = os.path.join(INCLUDE, HEADER_NAMES["sdg"])
 
-# every scalar type include/sde.h may use; any pointer is a c_void_p.  A type outside this map is an error
+# every scalar type the headers may use; any pointer is a c_void_p.  A type outside this map is an error
 # (parse_header raises), never a guess: a wrong width is a silent miscall.
 CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64,
           "float": ctypes.c_float, "double": ctypes.c_double}
-_PROTOTYPE = re.compile(r"([\w\s\*]+?)\b(sde_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
 _NUMBER = re.compile(r"(-?\d+)|(-?\d+\.\d*(?:[eE][-+]?\d+)?)f?")
 
 
@@ -31,50 +33,60 @@ def _strip_comments(text: str) -> str:
     return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
 
 
-def _ctype(decl: str, name: str, returns: bool = False):
+def _ctype(decl: str, name: str, returns: bool = False, header: str = "include/sde.h"):
     """The ctypes type of one declaration (`const float *fl`, `int64_t npix`, a bare return type)."""
     words = decl.replace("*", " * ").split()
     if "*" in words:
         return ctypes.c_char_p if returns and words[:-1] == ["const", "char"] else ctypes.c_void_p
     base = [w for w in (words if returns else words[:-1]) if w != "const"]
     if len(base) != 1 or base[0] not in CTYPES:
-        raise TypeError(f"include/sde.h: {name}: no ctypes mapping for `{decl.strip()}`")
+        raise TypeError(f"{header}: {name}: no ctypes mapping for `{decl.strip()}`")
     return CTYPES[base[0]]
 
 
-def parse_header(text: str):
-    """Header text -> ({function: (restype, argtypes)}, {SDE_* constant: number}): the binding's only source.
-    Constants are the `#define SDE_X number` lines (an `f` suffix dropped) and the members of every enum."""
+def parse_header(text: str, prefix: str = "sde"):
+    """Header text -> ({function: (restype, argtypes)}, {constant: number}) for the functions `prefix`_name and
+    the constants PREFIX_NAME: the binding's only source.  Constants are the `#define PREFIX_X number` lines (an
+    `f` suffix dropped) and the members of every enum; `#define`s and prototypes of another prefix are passed
+    over."""
     text = _strip_comments(text)
+    hdr, cap = "include/" + HEADER_NAMES[prefix], prefix.upper()
     constants = {}
-    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(SDE_\w+)[ \t]+(\S.*?)[ \t]*$", text, flags=re.M):
+    for name, value in re.findall(rf"^[ \t]*#[ \t]*define[ \t]+({cap}_\w+)[ \t]+(\S.*?)[ \t]*$", text, flags=re.M):
         m = _NUMBER.fullmatch(value)
         if not m:
-            raise TypeError(f"include/sde.h: #define {name} {value}: not a number")
+            raise TypeError(f"{hdr}: #define {name} {value}: not a number")
         constants[name] = int(m.group(1)) if m.group(1) else float(m.group(2))
     for body in re.findall(r"\benum\b[^{;]*\{([^}]*)\}", text):
         for member in filter(None, (t.strip() for t in body.split(","))):
-            m = re.fullmatch(r"(SDE_\w+)\s*=\s*(-?\d+)", member)
+            m = re.fullmatch(rf"({cap}_\w+)\s*=\s*(-?\d+)", member)
             if not m:
-                raise TypeError(f"include/sde.h: enum member `{member}`: expected SDE_NAME = integer")
+                raise TypeError(f"{hdr}: enum member `{member}`: expected {cap}_NAME = integer")
             constants[m.group(1)] = int(m.group(2))
     signatures = {}
-    for ret, name, params in _PROTOTYPE.findall(re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)):
+    prototype = re.compile(rf"([\w\s\*]+?)\b({prefix}_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+    for ret, name, params in prototype.findall(re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)):
         params = [] if params.strip() in ("", "void") else params.split(",")
-        signatures[name] = (_ctype(ret, name, returns=True), [_ctype(p, name) for p in params])
+        signatures[name] = (_ctype(ret, name, True, hdr), [_ctype(p, name, False, hdr) for p in params])
     return signatures, constants
 
 
-def header_functions(path: str = HEADER):
-    """Names of the functions declared in include/sde.h, by a looser rule than parse_header's (any `sde_name(`
-    outside a comment): tests hold the two against each other, so a prototype the parser skips is noticed."""
+def header_functions(path: str = None, prefix: str = "sde"):
+    """Names of the functions `prefix`_name declared in a header (default: the header of that prefix), by a looser
+    rule than parse_header's (any `prefix_name(` outside a comment): tests hold the two against each other, so a
+    prototype the parser skips is noticed."""
+    if path is None:
+        path = os.path.join(INCLUDE, HEADER_NAMES[prefix])
     with open(path) as fh:
-        return sorted(set(re.findall(r"\b(sde_[a-z0-9_]+)\s*\(", _strip_comments(fh.read()))))
+        return sorted(set(re.findall(rf"\b({prefix}_[a-z0-9_]+)\s*\(", _strip_comments(fh.read()))))
 
 
 with open(HEADER) as _fh:
     SIGNATURES, CONSTANTS = parse_header(_fh.read())   # name -> (restype, argtypes); SDE_* name -> number
+with open(GEOM_HEADER) as _fh:
+    GEOM_SIGNATURES, GEOM_CONSTANTS = parse_header(_fh.read(), prefix="sdg")   # the same, sdg_* / SDG_*
 globals().update(CONSTANTS)   # _lib.SDE_LAYOUT_DHW, ... as module attributes
+globals().update(GEOM_CONSTANTS)
 
 
 class SdeError(RuntimeError):
@@ -87,7 +99,7 @@ def _load():
                           "(there is no CPU fallback)")
     lib = ctypes.CDLL(LIB)
     missing = []
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **GEOM_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1,7 +1,7 @@
 """Drop-in for the reference's match.py batch entry point (match.py:19-103).
 
     python -m scenedepthestimation_amd.match [-g GPUS] [--checkpoint PATH|synthetic] [--cpu-path]
-           [--subpixel] [--bilateral]
+           [--subpixel] [--bilateral] [--calib FILE [--depth-out DIR]]
 
 Loops over ``./test/left_{i}.jpg`` / ``right_{i}.jpg`` for i = 1..18 (match.py:46),
 builds the tower once (weights packed and uploaded once, like the single TF
@@ -10,7 +10,9 @@ graph of match.py:34-37), and writes ``./disparity/ld{i}.png`` as
 seconds as in match.py:71-75 and is printed at the end (the reference's print is
 commented out, match.py:95-103).  --subpixel / --bilateral switch on the parabola refinement and the 9x9
 bilateral filter the reference carries commented out (process_functional.py:813-819, :882-974); --bilateral
-belongs to the SGM path (it filters the median's output).
+belongs to the SGM path (it filters the median's output).  --calib FILE (new): the inputs are raw camera images
+of one rig, rectified on the device from the calibration FILE (rectify.StereoCalibration) before anything else sees
+them; --depth-out DIR then also writes ``DIR/depth{i}.pfm`` (rectify.Rectifier.depth).  Without them nothing changes.
 
 Multi-GPU (new; the reference has none): under torchrun every rank takes pairs
 i = rank+1, rank+1+N, ... (pair data-parallel, no collective).
@@ -23,7 +25,7 @@ import sys
 
 import numpy as np
 
-from .match_single import DEFAULT_CKPT, normalise
+from .match_single import DEFAULT_CKPT, normalise, rectified_pair, write_depth
 
 
 def build_parser():
@@ -40,6 +42,9 @@ def build_parser():
     p.add_argument("--subpixel", action="store_true", help="parabola refinement of the winner (off in the reference)")
     p.add_argument("--bilateral", action="store_true",
                    help="9x9 bilateral filter after the median (off in the reference; SGM path only)")
+    p.add_argument("--calib", type=str, default=None,
+                   help="stereo calibration (.npz / .json): the inputs are raw images, rectified on the device")
+    p.add_argument("--depth-out", type=str, default=None, help="with --calib: a directory for depth{i}.pfm")
     return p
 
 
@@ -48,6 +53,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.bilateral and args.cpu_path:
         parser.error("--bilateral filters the median's output: it belongs to the SGM path")
+    if args.depth_out and not args.calib:
+        parser.error("--depth-out needs --calib (depth comes from the calibration's Q)")
     if "WORLD_SIZE" not in os.environ:
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu     # match.py:24 (CUDA_VISIBLE_DEVICES)
     import torch
@@ -60,13 +67,18 @@ def main(argv=None):
     rank, world, _ = init_from_env()
     weights = mc_cnn.load_weights(args.checkpoint, 5)
     detail_time = np.zeros(shape=[7], dtype=np.float32)
-    matcher = None
+    matcher = rectifier = None
+    if args.calib:
+        from .rectify import Rectifier, StereoCalibration
+        rectifier = Rectifier(StereoCalibration.load(args.calib))
     for i in [k + 1 for k in pairs_for_rank(args.pairs, world, rank)]:
         lp = os.path.join(args.image_path, "left_{}.jpg".format(i))
         rp = os.path.join(args.image_path, "right_{}.jpg".format(i))
         _l, _r = imageio.imread_gray(lp), imageio.imread_gray(rp)
         if _l is None or _r is None:
             raise AttributeError(f"'NoneType' object has no attribute 'astype' (cannot read {lp} / {rp})")
+        if rectifier is not None:
+            _l, _r = rectified_pair(rectifier, _l, _r)
         H, W = _l.shape
         if matcher is None or (matcher.H, matcher.W) != (H, W):
             matcher = StereoMatcher(H, W, args.ndisp, weights=weights, subpixel=args.subpixel,
@@ -91,6 +103,9 @@ def main(argv=None):
             disp = dl.cpu().numpy()
             add_detail_time(detail_time, timings)
         imageio.imwrite(os.path.join(args.out_path, "ld{}.png".format(i)), disp.astype("uint8") * 2)
+        if rectifier is not None and args.depth_out:
+            os.makedirs(args.depth_out, exist_ok=True)
+            write_depth(rectifier, disp, os.path.join(args.depth_out, "depth{}.pfm".format(i)))
     n = max(1, len(pairs_for_rank(args.pairs, world, rank)))
     names = ["computing features", "computing cost volume", '"*" cost aggregation', "SGM",
              "WTA & Subpixel refinement", "LR Check", "Filtering"]

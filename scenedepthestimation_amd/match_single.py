@@ -2,7 +2,7 @@
 
     python -m scenedepthestimation_amd.match_single [-g GPU] [-i ID] [-f FILE]
            [--checkpoint PATH|synthetic] [--cpu-path [--lr-check]] [--ndisp N] [--ui]
-           [--subpixel] [--bilateral]
+           [--subpixel] [--bilateral] [--calib FILE [--depth-out PATH]]
 
 Same flags, paths and outputs as match_single.py:15-57 (and, with --ui,
 match_single_ui.py:20-58): reads ``./eval/left_{id}.png`` / ``right_{id}.png``
@@ -22,6 +22,11 @@ the 5x5 median of process_functional.py:977-1088, :840-879).
 on the winner's two neighbours (process_functional.py:813-819) and the 9x9 bilateral filter of the median's
 output (:882-974).  Both are off by default; --bilateral needs a path that has a median (the SGM path or
 --cpu-path --lr-check).  The written PNG is still ``uint8(disparity)``.
+
+--calib FILE (new; the reference rectifies beforehand with OpenCV, Calibration/mycalibration.cpp:826-839): the two
+inputs are raw camera images and FILE a calibration (rectify.StereoCalibration: .npz or .json); the pair is rectified
+on the device before anything else sees it.  --depth-out PATH then also writes the depth of the result
+(rectify.Rectifier.depth, 0 where there is no disparity) as a one-channel .pfm.  Without them nothing changes.
 """
 from __future__ import annotations
 
@@ -52,7 +57,27 @@ def build_parser(ui: bool = False):
                    help="parabola refinement of the winner (process_functional.py:813-819, off in the reference)")
     p.add_argument("--bilateral", action="store_true",
                    help="9x9 bilateral filter after the median (process_functional.py:882-974, off in the reference)")
+    p.add_argument("--calib", type=str, default=None,
+                   help="stereo calibration (.npz / .json): the inputs are raw images, rectified on the device")
+    p.add_argument("--depth-out", type=str, default=None, help="with --calib: write the depth map as a .pfm")
     return p
+
+
+def rectified_pair(rectifier, left_raw, right_raw):
+    """Two raw host u8 images -> the rectified host pair (one upload, one remap launch, one download)."""
+    import torch
+    raw2 = torch.from_numpy(np.ascontiguousarray(np.stack([left_raw, right_raw]), np.uint8)).to(rectifier.device)
+    pair = rectifier.remap(raw2).cpu().numpy()
+    return pair[0], pair[1]
+
+
+def write_depth(rectifier, disp, path):
+    """Host disparity map -> rectifier.depth on the device -> one-channel .pfm."""
+    import torch
+
+    from . import pfm
+    d = torch.from_numpy(np.ascontiguousarray(disp, np.float32)).to(rectifier.device)
+    pfm.save_pfm(path, rectifier.depth(d).cpu().numpy())
 
 
 def normalise(img_f32):
@@ -68,6 +93,8 @@ def parse_args(argv=None, ui: bool = False):
         p.error("--lr-check needs --cpu-path (the SGM path has its own left-right check)")
     if args.bilateral and args.cpu_path and not args.lr_check:
         p.error("--bilateral filters the median's output: use the SGM path or --cpu-path --lr-check")
+    if args.depth_out and not args.calib:
+        p.error("--depth-out needs --calib (depth comes from the calibration's Q)")
     return args
 
 
@@ -106,6 +133,11 @@ def run(args) -> str:
     if _left is None or _right is None:
         # cv2.imread returns None and the reference then fails on `.astype` (AttributeError)
         raise AttributeError(f"'NoneType' object has no attribute 'astype' (cannot read {lp} / {rp})")
+    rectifier = None
+    if getattr(args, "calib", None):
+        from .rectify import Rectifier, StereoCalibration
+        rectifier = Rectifier(StereoCalibration.load(args.calib))
+        _left, _right = rectified_pair(rectifier, _left, _right)
     left = normalise(_left.astype(np.float32))
     right = normalise(_right.astype(np.float32))
     subpixel, bilateral = getattr(args, "subpixel", False), getattr(args, "bilateral", False)
@@ -129,6 +161,8 @@ def run(args) -> str:
     out = disp.astype("uint8") * 2 if args.ui else disp.astype("uint8")
     path = "./result/{}/ld{}.png".format(args.file, args.id)
     imageio.imwrite(path, out)
+    if rectifier is not None and getattr(args, "depth_out", None):
+        write_depth(rectifier, disp, args.depth_out)
     return path
 
 

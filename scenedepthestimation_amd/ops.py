@@ -1002,3 +1002,65 @@ def bad_pixels(disp, gt, threshold: float = 1.0, counts=None, area=None):
     check(lib.sde_bad_pixels(_need(disp, "disp"), _need(gt, "gt"), H, W, float(threshold),
                              _need(counts, "counts", dtype=torch.int32, shape=(2,)), pa, _stream()), "sde_bad_pixels")
     return counts
+
+
+# ----------------------------------------------------------------------------
+# geometry stage (include/sde_geom.h): rectification maps, remap, reprojection
+# ----------------------------------------------------------------------------
+NO_SAMPLE = _lib.SDG_NO_SAMPLE
+
+
+def _host_f64(a, n: int, name: str):
+    a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    if a.size != n:
+        raise ValueError(f"{name} must hold {n} numbers (got {a.size})")
+    return a
+
+
+def rectify_map(cal, H: int, W: int, out=None, device=None):
+    """The int32 [H,W,2] sampling map of one camera in 1/32 pixel (sdg_rectify_map) from `cal`, 26 host float64:
+    K (9), dist (8), inverse of P[:, :3] @ R (9).  out: a device tensor to fill, else one is made on `device`."""
+    cal = _host_f64(cal, 26, "cal")
+    if out is None:
+        out = torch.empty((H, W, 2), dtype=torch.int32, device=device if device is not None else "cuda")
+    check(lib.sdg_rectify_map(cal.ctypes.data, int(H), int(W), _need(out, "map", dtype=torch.int32, shape=(H, W, 2)),
+                              _stream()), "sdg_rectify_map")
+    return out
+
+
+def remap_u8(src, maps, out=None, valid=None):
+    """u8 [N,Hs,Ws] sources through int32 [N,H,W,2] maps -> u8 [N,H,W] (sdg_remap_u8), image i through map i, one
+    launch.  valid: optional u8 [N,H,W], 1 where every tap read was inside the source."""
+    if src.dim() != 3 or maps.dim() != 4 or maps.shape[0] != src.shape[0] or maps.shape[3] != 2:
+        raise ValueError(f"src must be [N,Hs,Ws] and maps [N,H,W,2], got {tuple(src.shape)} / {tuple(maps.shape)}")
+    N, Hs, Ws = src.shape
+    _, H, W, _ = maps.shape
+    if out is None:
+        out = _empty((N, H, W), torch.uint8, src)
+    po = _need(out, "out", dtype=torch.uint8, shape=(N, H, W))
+    ps = _need(src, "src", dtype=torch.uint8)
+    if ps < po + N * H * W and po < ps + N * Hs * Ws:
+        raise ValueError("out must not overlap src")
+    pv = None if valid is None else _need(valid, "valid", dtype=torch.uint8, shape=(N, H, W))
+    check(lib.sdg_remap_u8(ps, N, Hs, Ws, _need(maps, "maps", dtype=torch.int32), H, W, po, pv, _stream()),
+          "sdg_remap_u8")
+    return out
+
+
+def reproject(disp, Q, min_disp: float = 0.0, depth=None, xyz=None, want=("depth",)):
+    """f32 [H,W] disparities through the 4x4 matrix Q (16 host float64) -> (depth f32 [H,W], xyz f32 [H,W,3])
+    (sdg_reproject); an output is computed when given or named in `want`, else None.  Pixels that are not finite
+    or not above min_disp get 0."""
+    if disp.dim() != 2:
+        raise ValueError(f"disp must be [H,W], got {tuple(disp.shape)}")
+    H, W = disp.shape
+    Q = _host_f64(Q, 16, "Q")
+    if depth is None and "depth" in want:
+        depth = _empty((H, W), torch.float32, disp)
+    if xyz is None and "xyz" in want:
+        xyz = _empty((H, W, 3), torch.float32, disp)
+    pd = None if depth is None else _need(depth, "depth", shape=(H, W))
+    px = None if xyz is None else _need(xyz, "xyz", shape=(H, W, 3))
+    check(lib.sdg_reproject(_need(disp, "disp"), H, W, Q.ctypes.data, float(min_disp), pd, px, _stream()),
+          "sdg_reproject")
+    return depth, xyz

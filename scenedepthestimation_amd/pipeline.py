@@ -132,6 +132,7 @@ class StereoMatcher:
         self.packed = torch.from_numpy(packed).to(dev)
         self.img_u82 = torch.empty((2, H, W), dtype=torch.uint8, device=dev)
         self.img_u8 = [self.img_u82[0], self.img_u82[1]]
+        self.raw_u82 = None    # the unrectified pair of load_raw, allocated on first use
         # both images in one allocation: the tower runs the pair per launch (sde_tower_forward_batch)
         self.img_pad2 = torch.empty((2, H + 2 * L, W + 2 * L), dtype=torch.float32, device=dev)
         self.img_pad = [self.img_pad2[0], self.img_pad2[1]]
@@ -183,6 +184,19 @@ class StereoMatcher:
     def load_images(self, left_u8, right_u8):
         """Host u8 [H,W] arrays (or device tensors) -> resident device images."""
         ops.upload_u8_pair(self.img_u82, left_u8, right_u8)
+
+    def load_raw(self, left_raw, right_raw, rectifier):
+        """Raw (unrectified) host u8 arrays or device tensors of the rectifier's raw size -> the resident pair,
+        rectified on the device in one launch (rectify.Rectifier.remap into img_u82).  The raw pair's device
+        buffer is allocated on the first call; everything after it is what load_images leaves behind."""
+        if tuple(rectifier.out_size) != (self.H, self.W):
+            raise ValueError(f"the rectifier writes {tuple(rectifier.out_size)} images, this matcher takes "
+                             f"{(self.H, self.W)}")
+        shape = (2,) + tuple(rectifier.raw_size)
+        if self.raw_u82 is None or tuple(self.raw_u82.shape) != shape:
+            self.raw_u82 = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        ops.upload_u8_pair(self.raw_u82, left_raw, right_raw)
+        rectifier.remap(self.raw_u82, out=self.img_u82)
 
     def load_normalised(self, left, right):
         """Two normalised host images f32 [H,W] -> the tower's zero-padded input (process_functional.py:13-19),
