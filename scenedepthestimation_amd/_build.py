@@ -50,7 +50,8 @@ def sources():
 
 def _headers_mtime():
     hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hs += [os.path.join(INCLUDE, "sde.h"), os.path.join(INCLUDE, "sde_geom.h")]
+    hs += [os.path.join(INCLUDE, "sde.h"), os.path.join(INCLUDE, "sde_geom.h"),
+           os.path.join(INCLUDE, "sde_filter.h")]
     return max(os.path.getmtime(h) for h in hs)
 
 

@@ -3,6 +3,7 @@
     python -m scenedepthestimation_amd.match_single [-g GPU] [-i ID] [-f FILE]
            [--checkpoint PATH|synthetic] [--cpu-path [--lr-check]] [--ndisp N] [--ui]
            [--subpixel] [--bilateral] [--calib FILE [--depth-out PATH]]
+           [--speckle-size N [--speckle-range X]]
 
 Same flags, paths and outputs as match_single.py:15-57 (and, with --ui,
 match_single_ui.py:20-58): reads ``./eval/left_{id}.png`` / ``right_{id}.png``
@@ -27,6 +28,10 @@ output (:882-974).  Both are off by default; --bilateral needs a path that has a
 inputs are raw camera images and FILE a calibration (rectify.StereoCalibration: .npz or .json); the pair is rectified
 on the device before anything else sees it.  --depth-out PATH then also writes the depth of the result
 (rectify.Rectifier.depth, 0 where there is no disparity) as a one-channel .pfm.  Without them nothing changes.
+
+--speckle-size N (new; 0 = off) removes, as the last stage of whichever path runs, every region of at most N pixels
+of the map as matched whose 4-neighbours differ by at most --speckle-range (default 1.0; include/sde_filter.h): its
+pixels become -1, which the PNG's uint8 cast shows as 255 and --depth-out as depth 0.
 """
 from __future__ import annotations
 
@@ -35,6 +40,8 @@ import os
 import sys
 
 import numpy as np
+
+from .local_method import add_speckle_flags, speckle_option
 
 DEFAULT_CKPT = r"./check_points_11_11/model_epoch14.ckpt"   # match_single.py:46
 
@@ -60,6 +67,7 @@ def build_parser(ui: bool = False):
     p.add_argument("--calib", type=str, default=None,
                    help="stereo calibration (.npz / .json): the inputs are raw images, rectified on the device")
     p.add_argument("--depth-out", type=str, default=None, help="with --calib: write the depth map as a .pfm")
+    add_speckle_flags(p)
     return p
 
 
@@ -80,6 +88,15 @@ def write_depth(rectifier, disp, path):
     pfm.save_pfm(path, rectifier.depth(d).cpu().numpy())
 
 
+def speckle_filtered(disp, speckle):
+    """Host disparity map -> ops.speckle on the device -> host map (regions of at most speckle[0] pixels -> -1)."""
+    import torch
+
+    from . import ops
+    d = torch.from_numpy(np.ascontiguousarray(disp, np.float32)).cuda()
+    return ops.speckle(d, speckle[0], speckle[1], out=d)[0].cpu().numpy()
+
+
 def normalise(img_f32):
     """match_single.py:40-43: per-image (I - mean) / std over axes (0,1), then a channel axis."""
     x = (img_f32 - np.mean(img_f32, axis=(0, 1))) / np.std(img_f32, axis=(0, 1))
@@ -95,13 +112,15 @@ def parse_args(argv=None, ui: bool = False):
         p.error("--bilateral filters the median's output: use the SGM path or --cpu-path --lr-check")
     if args.depth_out and not args.calib:
         p.error("--depth-out needs --calib (depth comes from the calibration's Q)")
+    args.speckle = speckle_option(p, args)
     return args
 
 
-def lr_checked_disparity(left, right, ndisp, checkpoint, subpixel=False, bilateral=False, left_u8=None):
+def lr_checked_disparity(left, right, ndisp, checkpoint, subpixel=False, bilateral=False, left_u8=None,
+                         speckle=None):
     """The --lr-check map: compute_feature's tower on the normalised images (the same padded input, so the same
     features as the plain --cpu-path run), then StereoMatcher.lr_checked on them.  bilateral=True needs the left
-    u8 image (the filter's intensities)."""
+    u8 image (the filter's intensities); speckle: StereoMatcher's option."""
     import torch
 
     from . import mc_cnn
@@ -109,7 +128,7 @@ def lr_checked_disparity(left, right, ndisp, checkpoint, subpixel=False, bilater
     nlayers = 11 // 2
     H, W = left.shape[:2]
     m = StereoMatcher(H, W, ndisp, weights=mc_cnn.load_weights(checkpoint, nlayers), nlayers=nlayers,
-                      subpixel=subpixel, bilateral=bilateral)
+                      subpixel=subpixel, bilateral=bilateral, speckle=speckle)
     if bilateral:
         m.img_u8[0].copy_(torch.from_numpy(np.ascontiguousarray(left_u8, np.uint8)))
     m.load_normalised(left[..., 0], right[..., 0])
@@ -141,8 +160,9 @@ def run(args) -> str:
     left = normalise(_left.astype(np.float32))
     right = normalise(_right.astype(np.float32))
     subpixel, bilateral = getattr(args, "subpixel", False), getattr(args, "bilateral", False)
+    speckle = getattr(args, "speckle", None)
     if args.cpu_path and getattr(args, "lr_check", False):
-        disp = lr_checked_disparity(left, right, args.ndisp, args.checkpoint, subpixel, bilateral, _left)
+        disp = lr_checked_disparity(left, right, args.ndisp, args.checkpoint, subpixel, bilateral, _left, speckle)
     else:
         fl, fr = compute_feature(left, right, 11, 11, 64, args.checkpoint)
         if args.cpu_path and subpixel:
@@ -158,6 +178,8 @@ def run(args) -> str:
             detail_time = np.zeros(shape=[7], dtype=np.float32)
             disp, _, detail_time = disparity_compute_by_gpu(_left, _right, fl, fr, detail_time, ndisp=args.ndisp,
                                                             subpixel=subpixel, bilateral=bilateral)
+        if speckle is not None:
+            disp = speckle_filtered(disp, speckle)
     out = disp.astype("uint8") * 2 if args.ui else disp.astype("uint8")
     path = "./result/{}/ld{}.png".format(args.file, args.id)
     imageio.imwrite(path, out)

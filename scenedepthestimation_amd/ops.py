@@ -1064,3 +1064,39 @@ def reproject(disp, Q, min_disp: float = 0.0, depth=None, xyz=None, want=("depth
     check(lib.sdg_reproject(_need(disp, "disp"), H, W, Q.ctypes.data, float(min_disp), pd, px, _stream()),
           "sdg_reproject")
     return depth, xyz
+
+
+# ---------------------------------------------------------------- filters (include/sde_filter.h)
+def speckle_workspace_bytes(H: int, W: int) -> int:
+    """Bytes of sdf_speckle's workspace for an H x W map (sdf_speckle_workspace_bytes)."""
+    return int(lib.sdf_speckle_workspace_bytes(int(H), int(W)))
+
+
+def speckle(disp, max_size: int, max_diff: float = 1.0, fill: float = -1.0, out=None, mask=None, sizes=None,
+            want=("out",), workspace=None):
+    """Speckle removal of an f32 [H,W] disparity map (sdf_speckle) -> (out f32, mask u8, sizes i32), each [H,W]:
+    the regions of 4-connected valid (finite, >= 0) pixels whose neighbours differ by at most max_diff are
+    labelled on the device, and every region of at most max_size pixels is set to `fill` in out and to 1 in mask;
+    sizes holds each valid pixel's region size.  out is always computed (out=disp filters in place); mask and
+    sizes when given or named in `want`, else None.  workspace: a GPU tensor of speckle_workspace_bytes(H, W)
+    bytes, 4-byte aligned, contents arbitrary; one is allocated when absent."""
+    if disp.dim() != 2:
+        raise ValueError(f"disp must be [H,W], got {tuple(disp.shape)}")
+    H, W = disp.shape
+    if out is None:
+        out = _empty((H, W), torch.float32, disp)
+    if mask is None and "mask" in want:
+        mask = _empty((H, W), torch.uint8, disp)
+    if sizes is None and "sizes" in want:
+        sizes = _empty((H, W), torch.int32, disp)
+    n = speckle_workspace_bytes(H, W)
+    if workspace is None:
+        workspace = _empty((n,), torch.uint8, disp)
+    elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("speckle workspace must be a contiguous GPU tensor")
+    pm = None if mask is None else _need(mask, "mask", dtype=torch.uint8, shape=(H, W))
+    ps = None if sizes is None else _need(sizes, "sizes", dtype=torch.int32, shape=(H, W))
+    check(lib.sdf_speckle(_need(disp, "disp"), H, W, int(max_size), float(max_diff), float(fill),
+                          _need(out, "out", shape=(H, W)), pm, ps, workspace.data_ptr(),
+                          workspace.numel() * workspace.element_size(), _stream()), "sdf_speckle")
+    return out, mask, sizes

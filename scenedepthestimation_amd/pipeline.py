@@ -92,6 +92,42 @@ def tower_steps(img_pad, packed, nlayers: int, out, ws, precision: str = "f16x3"
         cur ^= 1
 
 
+class SpeckleStage:
+    """Speckle removal (ops.speckle, include/sde_filter.h) as the last stage of a path: regions of at most max_size
+    4-connected valid pixels whose neighbours differ by at most max_diff become -1 ("no winner"), which
+    rectify.Rectifier.depth / .points with the default min_disp = 0 turn into depth 0 / no point.  The filtered
+    maps (one per slot: a path that returns two maps filters each into its own), the last call's mask and region
+    sizes and the workspace are allocated on first use."""
+
+    def __init__(self, H, W, device, max_size, max_diff: float = 1.0):
+        self.H, self.W, self.device = int(H), int(W), torch.device(device)
+        self.max_size, self.max_diff = int(max_size), float(max_diff)
+        if self.max_size < 0 or not 0.0 <= self.max_diff < float("inf"):
+            raise ValueError("speckle=(max_size, max_diff) needs max_size >= 0 and a finite max_diff >= 0")
+        self.out, self.mask, self.sizes, self.ws = {}, None, None, None
+
+    @classmethod
+    def make(cls, H, W, device, speckle):
+        """None, a (max_size, max_diff) pair or a stage to share -> None or a stage."""
+        if speckle is None or isinstance(speckle, cls):
+            return speckle
+        max_size, max_diff = speckle
+        return cls(H, W, device, max_size, max_diff)
+
+    def run(self, disp, slot: int = 0):
+        """-> the filtered map, in this stage's buffer for `slot`; disp is left as it is."""
+        H, W, dev = self.H, self.W, self.device
+        if self.ws is None:
+            self.mask = torch.empty((H, W), dtype=torch.uint8, device=dev)
+            self.sizes = torch.empty((H, W), dtype=torch.int32, device=dev)
+            self.ws = torch.empty((ops.speckle_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
+        if slot not in self.out:
+            self.out[slot] = torch.empty((H, W), dtype=torch.float32, device=dev)
+        ops.speckle(disp, self.max_size, self.max_diff, -1.0, out=self.out[slot], mask=self.mask, sizes=self.sizes,
+                    workspace=self.ws)
+        return self.out[slot]
+
+
 def run_tower(img_pad, packed, nlayers, out, ws, precision="f16x3", nf=64, combine=None, on_launch=None):
     """Drive tower_steps to the end; combine(words) is applied at every yield (e.g. an all-reduce)."""
     for _stage, words in tower_steps(img_pad, packed, nlayers, out, ws, precision, nf, on_launch):
@@ -105,7 +141,7 @@ class StereoMatcher:
                  nf: int = 64, device=None, d_range=None, sgm: bool = False, tower_precision: str = "f16x3",
                  cv_mode: str = "certified", cbca_iters: int = 0, cbca_L1: int = 14, cbca_tau: float = 0.02,
                  emit_split: bool = False, sgm_placement_trials: int = SGM_PLACEMENT_TRIALS,
-                 subpixel: bool = False, bilateral: bool = False):
+                 subpixel: bool = False, bilateral: bool = False, speckle=None):
         self.H, self.W, self.D = int(height), int(width), int(ndisp)
         # the two stages the reference carries switched off (process_functional.py:813-819, :882-974); off by
         # default, and with both off every call below makes the launches it made before they existed
@@ -124,6 +160,10 @@ class StereoMatcher:
             # merged map instead (ops.cv_subpixel over the whole range)
             raise ValueError(f"subpixel=True needs the whole disparity range [0, {self.D}); this matcher holds "
                              f"the shard [{self.d0}, {self.d1})")
+        if speckle is not None and (self.d0, self.d1) != (0, self.D):
+            # a shard's map is not the final one: a region may exist only after the merge
+            raise ValueError(f"speckle needs the whole disparity range [0, {self.D}); this matcher holds the shard "
+                             f"[{self.d0}, {self.d1}): filter the merged map instead (ops.speckle)")
         w = mc_cnn.load_weights(weights, self.nlayers)
         hw, hb = mc_cnn.layer_lists(w, self.nlayers)
         packed = ops.pack_tower_weights(hw, hb)
@@ -154,10 +194,14 @@ class StereoMatcher:
             if (emit_split and cv_mode == "certified" and nlayers >= 2) else None
         self.split_valid = False
         self.lr_bufs = None    # the right view and the checked path's maps, allocated on first use (_lr_bufs)
+        # speckle=(max_size, max_diff): speckle removal as the last stage of every path (SpeckleStage, one shared
+        # by the paths); None (the default) leaves every path's launches and allocations as they are
+        self.speckle = SpeckleStage.make(H, W, dev, speckle)
         # the GPU path of disparity_compute_by_gpu; its aggregation stage borrows the tower's input buffers for
         # the z-normalised images
         self.sgm = SgmPath(H, W, self.D, dev, self.cbca_iters, self.cbca_L1, self.cbca_tau, self.subpixel,
-                           self.bilateral, self.sgm_placement_trials, scratch=(self.img_pad, self.stats, L))
+                           self.bilateral, self.sgm_placement_trials, scratch=(self.img_pad, self.stats, L),
+                           speckle=self.speckle)
         if sgm:
             self.sgm.alloc()
 
@@ -169,6 +213,17 @@ class StereoMatcher:
     @property
     def sgm_placement_ms(self):
         return self.sgm.placement_ms
+
+    @property
+    def speckle_mask(self):
+        """u8 [H,W], 1 where the last speckle filter call removed the pixel (None with the option off or before the
+        first call); rectify.Rectifier.depth of the filtered map is 0 there."""
+        return None if self.speckle is None else self.speckle.mask
+
+    @property
+    def speckle_sizes(self):
+        """i32 [H,W], the region size of every valid pixel of the last map filtered (None as speckle_mask)."""
+        return None if self.speckle is None else self.speckle.sizes
 
     @property
     def ws(self):
@@ -252,11 +307,14 @@ class StereoMatcher:
 
     def match(self):
         """One pass of the hot path on the resident images: features + fused CV/WTA -> disparity; with
-        subpixel=True followed by the parabola step on the winner's recomputed neighbours (ops.cv_subpixel)."""
+        subpixel=True followed by the parabola step on the winner's recomputed neighbours (ops.cv_subpixel).  With
+        speckle set the filtered map is returned, in a buffer of its own; self.disp keeps the unfiltered one."""
         self.features()
         self.cost_wta()
         if self.subpixel:
             ops.cv_subpixel(self.feat[0], self.feat[1], self.d0, self.d1, self.disp, "left", out=self.disp)
+        if self.speckle is not None:
+            return self.speckle.run(self.disp)
         return self.disp
 
     # -- left-right-checked fast path ------------------------------------------
@@ -269,7 +327,7 @@ class StereoMatcher:
             self.min_cost_r = torch.empty((H, W), dtype=torch.float32, device=dev)
             self.argmin_r = torch.empty((H, W), dtype=torch.int32, device=dev)
             self.cv_ws_r = torch.empty(ops.cv_wta_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
-            self.checked = CheckedPath(H, W, dev, self.bilateral)
+            self.checked = CheckedPath(H, W, dev, self.bilateral, self.speckle)
             self.lr_bufs = self.checked.bufs
         return self.lr_bufs
 
@@ -293,7 +351,7 @@ class StereoMatcher:
         """match_lr's stages after the features, on the features this matcher currently holds.  subpixel=True
         refines both views' raw maps before the check; bilateral=True filters the median's output with the left
         image (the reference's dead call, :1260, would filter the LRC-filled map and overwrite the median's
-        result: a documented divergence)."""
+        result: a documented divergence); speckle removal, when set, comes last."""
         self._need_whole_range()
         self._lr_bufs()
         self.cost_wta()
@@ -328,10 +386,12 @@ class StereoMatcher:
 class CheckedPath:
     """The reference's post-processing of two views' raw maps (is_error_match / LRC / median,
     process_functional.py:977-1088, :840-879) and the maps it writes: the wrap-free left-right check, LRC fill of
-    the left map, 5x5 median and, with bilateral=True, the 9x9 bilateral filter of the median's output.  Shared by
-    StereoMatcher.lr_checked and LocalMatcher.match_lr."""
+    the left map, 5x5 median and, with bilateral=True, the 9x9 bilateral filter of the median's output; with
+    speckle=(max_size, max_diff) (or a SpeckleStage to share) speckle removal of the map that would be returned.
+    Shared by StereoMatcher.lr_checked and LocalMatcher.match_lr."""
 
-    def __init__(self, H, W, device, bilateral: bool = False):
+    def __init__(self, H, W, device, bilateral: bool = False, speckle=None):
+        self.speckle = SpeckleStage.make(H, W, device, speckle)
         f32 = lambda: torch.empty((H, W), dtype=torch.float32, device=device)   # noqa: E731
         u8 = lambda: torch.empty((H, W), dtype=torch.uint8, device=device)      # noqa: E731
         self.bufs = dict(lrc=[u8(), u8()], filled=f32(), checked=f32())
@@ -347,10 +407,12 @@ class CheckedPath:
         # filled values
         b["checked"].copy_(b["filled"])
         ops.median5(b["filled"], b["checked"])
+        last = b["checked"]
         if "smoothed" in b:
-            ops.bilateral9(img_l, b["checked"], out=b["smoothed"])
-            return b["smoothed"], disp_r, b["lrc"][0]
-        return b["checked"], disp_r, b["lrc"][0]
+            last = ops.bilateral9(img_l, b["checked"], out=b["smoothed"])
+        if self.speckle is not None:
+            last = self.speckle.run(last)
+        return last, disp_r, b["lrc"][0]
 
 
 class SgmPath:
@@ -361,17 +423,19 @@ class SgmPath:
     cbca_iters > 0 puts cross-based aggregation (build-defined; 0 = the reference's path) before SGM; its arms come
     from the z-normalised images, which need scratch = (img_pad, stats, pad): two f32 [H+2p, W+2p] buffers and
     two ops.preprocess_scratch_bytes(H, W) scratch tensors (StereoMatcher lends the tower's input buffers).
-    subpixel / bilateral: the two stages the reference carries switched off (see run)."""
+    subpixel / bilateral: the two stages the reference carries switched off (see run).  speckle: None, a
+    (max_size, max_diff) pair or a SpeckleStage to share; with post=True the maps run() returns are filtered."""
 
     def __init__(self, height: int, width: int, ndisp: int, device, cbca_iters: int = 0, cbca_L1: int = 14,
                  cbca_tau: float = 0.02, subpixel: bool = False, bilateral: bool = False,
-                 placement_trials: int = SGM_PLACEMENT_TRIALS, scratch=None):
+                 placement_trials: int = SGM_PLACEMENT_TRIALS, scratch=None, speckle=None):
         self.H, self.W, self.D, self.device = int(height), int(width), int(ndisp), torch.device(device)
         self.cbca_iters, self.cbca_L1, self.cbca_tau = int(cbca_iters), int(cbca_L1), float(cbca_tau)
         self.subpixel, self.bilateral = bool(subpixel), bool(bilateral)
         self.placement_trials = int(placement_trials)
         self.placement_ms = None     # the SGM pair time of each placement draw (_place_volumes)
         self.scratch = scratch
+        self.speckle = SpeckleStage.make(self.H, self.W, self.device, speckle)
         self.bufs = None
 
     def _place_volumes(self, pen, disp):
@@ -540,7 +604,12 @@ class SgmPath:
             # LRC-filled map and overwrite the median's result (documented divergence).
             ops.bilateral9(img_l, b["disp"][0], out=b["disp_a"])
             ops.bilateral9(img_r, b["disp"][1], out=b["disp_b"])
-            mark("filter", t)
-            return b["disp_a"], b["disp_b"]
+            final = (b["disp_a"], b["disp_b"])
+        else:
+            final = (b["disp"][0], b["disp"][1])
+        if self.speckle is not None:
+            # the right map first: the stage's mask and sizes are then the left map's
+            right = self.speckle.run(final[1], slot=1)
+            final = (self.speckle.run(final[0], slot=0), right)
         mark("filter", t)
-        return b["disp"][0], b["disp"][1]
+        return final
