@@ -308,6 +308,11 @@ int sde_sgm_penalties(const uint8_t *img, int H, int W, double P1, double P2, in
  * UD-LR, DU-LR, UD-RL, DU-RL; fp64 recurrence, float32 S.  The caller zeroes S
  * (the reference uploads np.zeros, :1116-1119).  cv: [H][W][D] with invalid
  * voxels = 1.0 (sde_cost_volume HWD).  Requires H >= 2, W >= 2.
+ * pen: [H][W][16], from sde_sgm_penalties or the caller's own: any float32 values.  Finite
+ * penalties with P1 >= 0 (P2 of any sign) and finite costs run the fast recurrence; a scanline
+ * leaves it for the reference's exact arithmetic (slower, same values as the reference, bit for
+ * bit including zero signs) from its first step on with a NaN / inf cost or penalty, a P1 < 0,
+ * or -- when S is the caller's -- a voxel whose cost and S are both -0.0.
  */
 int sde_sgm_8path(const float *cv, const float *pen, int H, int W, int D, float *S, void *stream);
 
@@ -322,9 +327,11 @@ int sde_sgm_8path(const float *cv, const float *pen, int H, int W, int D, float 
 /* The caller asserts that penalty channels 0/1 are zero (sde_sgm_penalties never writes
  * them, as the reference's sgm_penelty_kernel): direction DU then reduces to S += C (+0.0
  * off its first row) for finite costs and is folded into the UD pass (7 passes instead of
- * 8, same values).  A column holding a non-finite cost, or a non-finite UD penalty
- * (channels 2/3), is detected and recomputed for both directions in the reference's exact
- * arithmetic, so the fold gives the unfolded values for any costs. */
+ * 8, same values).  A column holding a non-finite cost, a non-finite or negative UD P1 or
+ * non-finite UD P2 (channels 2/3) or, with SDE_SGM_ACCUMULATE, a voxel whose cost and S are
+ * both -0.0, is detected and recomputed for both directions in the reference's exact
+ * arithmetic, so the fold gives the unfolded values for any costs, any S and any penalties
+ * in channels 2..15. */
 #define SDE_SGM_ZERO_DU_PENALTIES 2
 int sde_sgm_8path_pair(const float *cv_l, const float *pen_l, float *S_l, const float *cv_r, const float *pen_r,
                        float *S_r, int H, int W, int D, int flags, void *stream);

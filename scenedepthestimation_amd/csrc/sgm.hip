@@ -40,7 +40,8 @@ constexpr ScanForm form()
     return {FIRST, DU, WTA, VMIN, DC, DIRC, launch_form<DPL, VEC, FIRST, DU, WTA, VMIN, DC, DIRC>};
 }
 
-// Every kernel that can run is named here once: per DPL, the seven forms for any D and direction,
+// Every kernel that can run is named here once: per DPL, the seven forms for any D and direction (with
+// vector loads where DPL divides D, else scalar ones; launch_dpl never asks for <1, false>),
 //                             FIRST  DU     WTA    VMIN
 template <int DPL, bool VEC>
 constexpr ScanForm kForms[7] = {
@@ -85,7 +86,10 @@ template <int DPL>
 static bool launch_dpl(const SgmLaunch &L)
 {
     if (L.D == 64 * DPL && launch_first_match(kFormsFullD<DPL>, L)) return true;
-    return L.D % DPL == 0 ? launch_first_match(kForms<DPL, true>, L) : launch_first_match(kForms<DPL, false>, L);
+    // (DPL = 1: every D is a multiple -- the scalar-load forms are not instantiated)
+    if constexpr (DPL > 1)
+        if (L.D % DPL != 0) return launch_first_match(kForms<DPL, false>, L);
+    return launch_first_match(kForms<DPL, true>, L);
 }
 
 // SDE_ERR_ARG: D beyond 512, or a combination that is no form (no entry point asks for one)

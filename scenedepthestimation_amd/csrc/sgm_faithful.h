@@ -1,8 +1,11 @@
 // sgm_faithful.h -- the SGM recurrence in the reference's exact arithmetic: the slow path a scanline takes
-// from its first non-finite cost or penalty on.
+// from its first step on that the fast recurrence would not compute as the reference does: a non-finite cost or
+// penalty, a P1 below zero, or (accumulating onto a caller's S) a voxel whose cost and S are both -0.0.
 //
-// The fast recurrence (sgm_scan.h: min chain in any order, one wave-wide minimum) equals the reference's
-// for finite costs: its minima are then plain minima.  With NaN / inf in
+// The fast recurrence (sgm_scan.h: min chain in any order, one wave-wide minimum, no term for the missing
+// neighbour at d = 0 and D-1) equals the reference's for finite costs and penalties of any sign except P1 < 0,
+// up to the signs of zeros in L: its minima are then plain minima, L'(d) + P1 >= L'(d) makes the dropped term
+// idle, and a zero's sign in L reaches S only where S and the cost are both -0.0.  With NaN / inf in
 // the costs the reference's exact arithmetic decides where they propagate (SGM_Interation,
 // process_functional.py:265-343): Numba's binary min(a, b) = b if b < a else a (a NaN first
 // argument sticks, a NaN second one is ignored), the chain
@@ -11,8 +14,8 @@
 // reference lane of 4 disparities: min(min(c1, c2), min(c3, c4)), then an xor butterfly
 // min(m, shfl_xor(m, k)), k = 1, 2, 4, .. -- with NaN present lanes can end with different
 // minima, and each uses its own at the next step.  A line switches to this "faithful" step
-// (sticky) at the first step whose costs are not all finite: every earlier state is finite, so
-// it carries over exactly.  Generic D (the reference has D = 128 only): lanes of 4, missing
+// (sticky) at the first such step: the line is replayed from its start in this arithmetic and
+// stores from that step on (every S stored before it is the reference's).  Generic D (the reference has D = 128 only): lanes of 4, missing
 // disparities of the last lane and padding lanes up to a power of two act as +inf.
 #pragma once
 #include "sgm_wave.h"

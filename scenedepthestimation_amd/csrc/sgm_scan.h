@@ -8,7 +8,8 @@
 //   L(p,d) = C(p,d) + (min(L'(d), L'(d-1)+P1, L'(d+1)+P1, m'+P2') - m')   otherwise
 //   S(p,d) = f32(f64(S(p,d)) + L(p,d));   m = min_d L(p,d)
 // with P1 from the previous pixel's penalty channel, P2' read at the previous
-// step, out-of-range neighbours (d = 0, D-1) dropped, n-1 pixels per line of n
+// step, out-of-range neighbours (d = 0, D-1) dropped (the reference takes the voxel itself
+// there: the same minimum for P1 >= 0; a step with P1 < 0 goes faithful), n-1 pixels per line of n
 // (>= 2), and diagonal lines wrapping around the image with a path restart.
 //
 // Mapping: one wave64 (one workgroup) per scanline and image side, so the line,
@@ -160,15 +161,34 @@ struct SgmV {
     typedef float T __attribute__((ext_vector_type(N)));
 };
 
-// A cost or a penalty that is NaN or +-inf anywhere in the wave: the fast recurrence's minima are the
-// reference's for finite operands only.  c: DPL floats, an array or a vector.
+// A cost or a penalty anywhere in the wave that the fast recurrence does not treat as the reference does: NaN or
+// +-inf (its minima are the reference's for finite operands only), or a P1 below zero.  The reference's missing
+// neighbour at d = 0 and d = D-1 is the voxel itself, so its chain holds L'(d) + P1 there; the fast chain drops
+// that term, which is the same minimum only while P1 >= 0.  (P2 may have any sign: m' + P2 is one term in both.)
+// c: DPL floats, an array or a vector.
 template <int DPL, typename C>
 __device__ __forceinline__ bool any_nonfinite(const C &c, float p1, float p2)
 {
     bool nf = __builtin_amdgcn_classf(p1, 0x207) | __builtin_amdgcn_classf(p2, 0x207);   // s/qNaN, -inf, +inf
 #pragma unroll
     for (int i = 0; i < DPL; i++) nf |= __builtin_amdgcn_classf(c[i], 0x207);
-    return __builtin_amdgcn_ballot_w64(nf) != 0;
+    // p1 is wave-uniform: one scalar compare of its bits -- sign set and not -0.0 (a second class mask would
+    // cost every form a register)
+    return __builtin_amdgcn_ballot_w64(nf) != 0 || __float_as_uint(p1) > 0x80000000u;
+}
+
+// A voxel whose cost and incoming S are both -0.0, anywhere in the wave: the only way a zero's sign reaches S
+// (S + L = -0 needs both at -0, and L = C + x is -0 only for C = -0).  Which sign L's zero has there depends on
+// the order of the reference's minima over zeros of both signs (left, self, right, m + P2, and one minimum per
+// reference lane), which the fast chain (self first, one wave minimum) does not keep -- so the forms that
+// accumulate onto a caller's S send such a step to the faithful path.  S the library wrote itself holds no -0.0.
+template <int DPL, typename C>
+__device__ __forceinline__ bool any_negzero_pair(const C &c, const C &s)
+{
+    bool nz = false;
+#pragma unroll
+    for (int i = 0; i < DPL; i++) nz |= __float_as_uint(c[i]) == 0x80000000u && __float_as_uint(s[i]) == 0x80000000u;
+    return __builtin_amdgcn_ballot_w64(nz) != 0;
 }
 
 // WTA_and_SupixelRefinement_kernel (process_functional.py:800-837) on one pixel whose S values
@@ -311,14 +331,18 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
         // column whose costs are not all finite is found first and runs both directions in the
         // reference's arithmetic (the fold is exact for finite costs only)
         // (and the UD penalties, channels 2/3: the fast recurrence's minima are the reference's
-        // for finite operands only)
+        // for finite operands and P1 >= 0 only; and a voxel with cost and S both -0.0: DU's own L can
+        // be -0.0 there, which the fold's C + 0.0 never is)
         bool bad = false;
         for (int r = 0; r < H && !bad; r++) {
-            float c[DPL];
+            float c[DPL], s[DPL];
             const size_t px = (size_t)r * W + line, off = px * D;
 #pragma unroll
-            for (int i = 0; i < DPL; i++) c[i] = sd.cv[off + min(dbase + i, D - 1)];
-            bad = any_nonfinite<DPL>(c, sd.pen[px * 16 + 2], sd.pen[px * 16 + 3]);
+            for (int i = 0; i < DPL; i++) {
+                c[i] = sd.cv[off + min(dbase + i, D - 1)];
+                s[i] = sd.S[off + min(dbase + i, D - 1)];
+            }
+            bad = any_nonfinite<DPL>(c, sd.pen[px * 16 + 2], sd.pen[px * 16 + 3]) || any_negzero_pair<DPL>(c, s);
         }
         if (bad) {
             faithful_vertical<DPL>(sd.cv, sd.pen, sd.S, H, W, D, line, true, true, flds);
@@ -350,7 +374,7 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
     double L[DPL];
     double m = 1.0, mP2 = 1.0;
     float p1c = 0.0f;              // the previous step's pixel's P1 channel
-    int kf = -1;                   // first step with a non-finite cost: the line continues faithfully
+    int kf = -1;                   // first step the fast recurrence must not take: the line continues faithfully
     bool redo = false;             // DU fold (FIRST): recompute the column in the faithful arithmetic
 #pragma unroll
     for (int i = 0; i < DPL; i++) L[i] = 1.0;
@@ -376,9 +400,11 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
             p1c = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, sl.p1)));
             if (DU) {
                 if (FIRST && !redo) redo = any_nonfinite<DPL>(sl.c, p1f, p2f);
-            } else if (kf < 0 && k < g.n && any_nonfinite<DPL>(sl.c, p1f, p2f)) {
-                // every state so far is finite; from step k on the line is redone in the reference's
-                // exact arithmetic after this loop, which stores nothing more for it
+            } else if (kf < 0 && k < g.n &&
+                       (any_nonfinite<DPL>(sl.c, p1f, p2f) || (!VMIN && any_negzero_pair<DPL>(sl.c, sl.s)))) {
+                // every state so far is finite, and equal to the reference's up to the signs of zeros in L, which
+                // no S stored so far depends on; from step k on the line is redone in the reference's exact
+                // arithmetic after this loop, which stores nothing more for it
                 kf = k;
             }
             const bool keep = DU || kf < 0;
@@ -576,7 +602,7 @@ __global__ __launch_bounds__(64) void sgm_scan_kernel(SgmSide s0, SgmSide s1, in
         }
     }
     if (DU && FIRST && __builtin_amdgcn_ballot_w64(redo) != 0) {
-        // a non-finite cost in this column: the folded DU term is not the reference's -- redo UD
+        // a non-finite cost (or a UD penalty the fast recurrence must not take) in this column: redo UD
         // (overwrite) and DU (accumulate) in the faithful arithmetic
         faithful_vertical<DPL>(sd.cv, sd.pen, sd.S, H, W, D, line, true, false, flds);
         faithful_vertical<DPL>(sd.cv, sd.pen, sd.S, H, W, D, line, false, true, flds);

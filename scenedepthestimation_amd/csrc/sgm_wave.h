@@ -41,7 +41,12 @@ __device__ __forceinline__ int dpp_i32(int v)
 // is NaN (non-finite costs and penalties take the faithful path), and a zero's sign never
 // changes a magnitude downstream (x + -0 = x + +0 for x != 0; comparisons ignore it): it can
 // reach S only through S + L with S = -0, and S is never -0 unless the caller's accumulate
-// input holds one -- so the callers that accumulate onto a caller's S keep the selects.
+// input holds one.  The selects do not give the reference's zero signs either (its chain
+// prefers left, self, right, m + P2 on a tie and keeps a minimum per reference lane; this one
+// prefers self and has one wave minimum), so the forms that accumulate onto a caller's S send
+// a step that could show the difference -- a voxel with S and cost both -0.0 -- to the
+// faithful path (any_negzero_pair, sgm_scan.h); they keep the selects, whose result for
+// finite operands does not depend on the instruction's handling of zeros.
 template <bool VMIN = false>
 __device__ __forceinline__ double dmin(double a, double t)
 {
