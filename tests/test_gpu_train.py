@@ -21,6 +21,7 @@ BS, LS = (1, 5, 8, 67, 130), (1, 2, 5)
 # per batch size, the first seed >= 100 + B at which the float64 literal has an active triplet at every depth in LS
 # (found on the CPU; test_gradients asserts it), so that every case measures a gradient and none compares zeros
 SEEDS = {1: 106, 5: 106, 8: 108, 67: 167, 130: 230}
+SEEDS.update({259: 359, 440: 540})      # at L = 5 alone: the capped-chunk batches of test_gpu_train_edges.py
 
 
 def dev(a):

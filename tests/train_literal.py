@@ -23,7 +23,7 @@ def run(patches, weights, nlayers, margin=0.3, relu_masks=None, hinge_mask=None,
     """patches [3][B][P][P]; weights: dict of HWIO weights / biases.  relu_masks: list of nlayers - 1 arrays
     [3B][s][s][nf] (truthy = pass), hinge_mask: [B].  ->  dict with
         loss (float), h [B], feats [3B][nf], pre: the pre-activations z_k of layers 1..nlayers as [3B][s][s][nf],
-        grads: {variable name: array} (if grads)."""
+        grads: {variable name: array} and dpre: d loss / d z_k, shaped as pre (if grads)."""
     patches = np.asarray(patches)
     B, P = patches.shape[1], patches.shape[2]
     params = {}
@@ -31,9 +31,12 @@ def run(patches, weights, nlayers, margin=0.3, relu_masks=None, hinge_mask=None,
         params[wn] = torch.tensor(np.asarray(weights[wn]), dtype=dtype, requires_grad=grads)
         params[bn] = torch.tensor(np.asarray(weights[bn]), dtype=dtype, requires_grad=grads)
     x = torch.tensor(patches, dtype=dtype).reshape(3 * B, 1, P, P)
-    pre = []
+    pre, zs = [], []
     for k, (wn, bn) in enumerate(var_names(nlayers), start=1):
         z = F.conv2d(x, params[wn].permute(3, 2, 0, 1), params[bn])
+        if grads:
+            z.retain_grad()
+            zs.append(z)
         pre.append(z.detach().permute(0, 2, 3, 1).numpy().copy())
         if k < nlayers:
             if relu_masks is not None:
@@ -52,6 +55,7 @@ def run(patches, weights, nlayers, margin=0.3, relu_masks=None, hinge_mask=None,
     if grads:
         loss.backward()
         out["grads"] = {k: (v.grad.numpy().copy() if v.grad is not None else np.zeros(v.shape)) for k, v in params.items()}
+        out["dpre"] = [z.grad.permute(0, 2, 3, 1).numpy().copy() for z in zs]
     return out
 
 
