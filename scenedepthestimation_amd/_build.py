@@ -49,9 +49,7 @@ def sources():
 
 
 def _headers_mtime():
-    hs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hs += [os.path.join(INCLUDE, "sde.h"), os.path.join(INCLUDE, "sde_geom.h"),
-           os.path.join(INCLUDE, "sde_filter.h")]
+    hs = [os.path.join(d, f) for d in (CSRC, INCLUDE) for f in os.listdir(d) if f.endswith(".h")]
     return max(os.path.getmtime(h) for h in hs)
 
 

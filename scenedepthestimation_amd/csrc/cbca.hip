@@ -83,19 +83,6 @@ __global__ __launch_bounds__(256) void cbca_transpose_kernel(const uint32_t *__r
 // Cache policy of the cost streams (aux bit 1 = nt on gfx950): each voxel is read once and written
 // once per pass, so both ways are nontemporal (round 2: 1.513 -> 1.468 ms per pair iteration).
 constexpr int CB_NT = 2;
-constexpr uint32_t CB_OOB = 0x80000000u;    // a voffset past every range: load 0, store dropped
-
-// Buffer descriptor (wave-uniform inputs only) for raw dword loads/stores with a 32-bit per-lane
-// voffset, an SGPR soffset and the hardware range check on voffset (>= bytes: load 0, store
-// dropped; every range below is < 2^31, so a voffset of CB_OOB is always out of range).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t cb_rsrc(const void *base, uint32_t bytes)
-{
-    const uintptr_t b = (uintptr_t)base;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-    void *p = (void *)(((uintptr_t)hi << 32) | lo);
-    return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -174,10 +161,10 @@ __device__ __forceinline__ void cbca_h_item(const CbcaArgs &A, int y, int c, int
     const uint32_t D4 = 4u * (uint32_t)D;
     const uint32_t dl4 = 4u * (uint32_t)min(d, D - 1);
     const uint32_t rowbytes = 4u * (uint32_t)W * (uint32_t)D;
-    const __amdgpu_buffer_rsrc_t rc = cb_rsrc(A.src + (size_t)y * W * D, rowbytes);
-    const __amdgpu_buffer_rsrc_t rd = cb_rsrc(A.dst + (size_t)y * W * D, rowbytes);
-    const __amdgpu_buffer_rsrc_t ra = cb_rsrc(A.al + (size_t)y * W, 4u * W);
-    const __amdgpu_buffer_rsrc_t rb = cb_rsrc(A.ar + (size_t)y * W, 4u * W);
+    const __amdgpu_buffer_rsrc_t rc = buf_rsrc(A.src + (size_t)y * W * D, rowbytes);
+    const __amdgpu_buffer_rsrc_t rd = buf_rsrc(A.dst + (size_t)y * W * D, rowbytes);
+    const __amdgpu_buffer_rsrc_t ra = buf_rsrc(A.al + (size_t)y * W, 4u * W);
+    const __amdgpu_buffer_rsrc_t rb = buf_rsrc(A.ar + (size_t)y * W, 4u * W);
     // a lane stores output t iff t >= th = max(t0, d) (valid voxel of this segment) and d < D
     const int th = d < D ? max(t0, d) : 0x7FFFFFFF;
 
@@ -226,7 +213,7 @@ __device__ __forceinline__ void cbca_h_item(const CbcaArgs &A, int y, int c, int
         sld = opq_s(sld + D4);
         __builtin_amdgcn_sched_barrier(0);
         const float out = (float)(pb - pa);
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, out), rd, t >= th ? vst : CB_OOB, 0,
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, out), rd, t >= th ? vst : BUF_OOB, 0,
                                               CB_NT);
         vst = opq_v(vst + D4);
     };
@@ -320,12 +307,12 @@ __device__ __forceinline__ void cbca_v_item(const CbcaArgs &A, int x, int c, int
     // descriptors over the column, rebased on row fbase (loads) / fb - R - 1 (stores) every block, their
     // ranges covering the rows a block touches (< 2^31 bytes: the shape check)
     const uint32_t win = (uint32_t)(RS + PF + R + 1) * rowv;
-    const __amdgpu_buffer_rsrc_t ra = cb_rsrc(A.alT + (size_t)x * Hp, 4u * (uint32_t)Hp);
+    const __amdgpu_buffer_rsrc_t ra = buf_rsrc(A.alT + (size_t)x * Hp, 4u * (uint32_t)Hp);
     // right-image arms from the ROW-major copy: at a row, lane d reads column x - d, so the wave's
     // 64 lanes read 64 adjacent words (one 256-B run) -- the column-major copy made every dwordx4
     // a gather of 64 cache lines
-    const __amdgpu_buffer_rsrc_t rb = cb_rsrc(A.ar, 4u * (uint32_t)W * (uint32_t)H);
-    const uint32_t bcol = lane_ok ? 4u * (uint32_t)(x - d) : CB_OOB;
+    const __amdgpu_buffer_rsrc_t rb = buf_rsrc(A.ar, 4u * (uint32_t)W * (uint32_t)H);
+    const uint32_t bcol = lane_ok ? 4u * (uint32_t)(x - d) : BUF_OOB;
 
     float cr[PF];
     uint32_t Bq[RS];             // right-image arm of row fb + j (per lane); slot j is reloaded with
@@ -333,7 +320,7 @@ __device__ __forceinline__ void cbca_v_item(const CbcaArgs &A, int x, int c, int
     uint32_t A0, A1;             // left-image arm of row fb + lane (lanes < RS), pairs by block parity
     uint32_t sup[U];             // (vu | vd << 16) of the last U front positions
     auto arm_r = [&](int row) {  // row `row` of the right image at x - d (rows past H read 0)
-        const uint32_t off = bcol == CB_OOB ? CB_OOB : bcol + 4u * (uint32_t)W * (uint32_t)row;
+        const uint32_t off = bcol == BUF_OOB ? BUF_OOB : bcol + 4u * (uint32_t)W * (uint32_t)row;
         return __builtin_amdgcn_raw_buffer_load_b32(rb, off, 0, 0);
     };
     // the arms first: loop-carried registers loaded after the cost prefetch would make the entry
@@ -343,7 +330,7 @@ __device__ __forceinline__ void cbca_v_item(const CbcaArgs &A, int x, int c, int
 #pragma unroll
     for (int m = 0; m < RS; m++) Bq[m] = arm_r(fs + m);
     {
-        const __amdgpu_buffer_rsrc_t rc0 = cb_rsrc(A.src + ((size_t)fs * W + x) * D, win);
+        const __amdgpu_buffer_rsrc_t rc0 = buf_rsrc(A.src + ((size_t)fs * W + x) * D, win);
 #pragma unroll
         for (int j = 0; j < PF; j++)
             cr[j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
@@ -410,7 +397,7 @@ __device__ __forceinline__ void cbca_v_item(const CbcaArgs &A, int x, int c, int
         // (an invalid lane's count may be anything: clamped into the table)
         const cb_r rcp = CbV<R>::TAB ? tab[min(cnt, (uint32_t)CbV<R>::NT - 1)] : (cb_r)cb_recip(cnt);
         const float out = (float)(num * rcp);
-        const uint32_t vo = (lane_ok && t >= t0) ? 4u * (uint32_t)d : CB_OOB;
+        const uint32_t vo = (lane_ok && t >= t0) ? 4u * (uint32_t)d : BUF_OOB;
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, out), rd, vo, (int)sst, CB_NT);
         sst = opq_s(sst + rowv);
     };
@@ -421,8 +408,8 @@ __device__ __forceinline__ void cbca_v_item(const CbcaArgs &A, int x, int c, int
         // loads for positions fb + PF .. go against a descriptor rebased on row fbase (a tail block
         // may start past the last row), stores against one rebased on row fb - R - 1
         const int fbase = clamp ? min(fb, H - 1) : fb;
-        const __amdgpu_buffer_rsrc_t rc = cb_rsrc(A.src + ((size_t)fbase * W + x) * D, win);
-        const __amdgpu_buffer_rsrc_t rd = cb_rsrc(A.dst + ((size_t)(fb - R - 1) * W + x) * D, win);
+        const __amdgpu_buffer_rsrc_t rc = buf_rsrc(A.src + ((size_t)fbase * W + x) * D, win);
+        const __amdgpu_buffer_rsrc_t rd = buf_rsrc(A.dst + ((size_t)(fb - R - 1) * W + x) * D, win);
         uint32_t sld = rowv * (uint32_t)PF, sst = 0;
 #pragma unroll
         for (int j = 0; j < RS; j++)
@@ -517,8 +504,8 @@ __global__ __launch_bounds__(256) void cbca_rotate_kernel(const float *__restric
     const int nd = min(RT_ND, D - d0);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t rowbytes = 4u * (uint32_t)W * (uint32_t)D;
-    const __amdgpu_buffer_rsrc_t ri = cb_rsrc(in + (size_t)y * W * D, rowbytes);
-    const __amdgpu_buffer_rsrc_t ro = cb_rsrc(out + (size_t)y * W * D, rowbytes);
+    const __amdgpu_buffer_rsrc_t ri = buf_rsrc(in + (size_t)y * W * D, rowbytes);
+    const __amdgpu_buffer_rsrc_t ro = buf_rsrc(out + (size_t)y * W * D, rowbytes);
     // piece r (0 <= r < RT_NP + nd - 1): source pixel (x0 + base + r) mod W; output pixel p of relative
     // disparity e = d - d0 is p = r - e (S > 0) or p = r + e - (nd - 1) (S < 0)
     const int base = S > 0 ? d0 : -d0 - (nd - 1);
@@ -552,7 +539,7 @@ __global__ __launch_bounds__(256) void cbca_rotate_kernel(const float *__restric
             uint32_t vraw = 4u * ((uint32_t)q * D + d);
             asm volatile("" : "+v"(vraw));
             v[b] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                                                 ri, ok_m >= 0 ? vraw : CB_OOB, 0, CB_NT));
+                                                 ri, ok_m >= 0 ? vraw : BUF_OOB, 0, CB_NT));
             at[b] = in_m >= 0 ? p * RT_ND + e : RT_NP * RT_ND + lane;
         }
 #pragma unroll
@@ -570,7 +557,7 @@ __global__ __launch_bounds__(256) void cbca_rotate_kernel(const float *__restric
             const int p = i0 + 4 * b + wave, x = x0 + p, d = d0 + lane;
             const bool inr = x < W && lane < nd;
             v[b] = rbuf[p * RT_ND + lane];
-            vo[b] = inr && (!valid_only || x + d < W) ? 4u * ((uint32_t)x * D + d) : CB_OOB;
+            vo[b] = inr && (!valid_only || x + d < W) ? 4u * ((uint32_t)x * D + d) : BUF_OOB;
         }
 #pragma unroll
         for (int b = 0; b < WB; b++)
@@ -596,13 +583,13 @@ static size_t cbca_ws_bytes(int H, int W) { return sizeof(uint32_t) * (size_t)cb
 template <typename K>
 static int cb_resident(std::atomic<int> (&cache)[64], K kernel, int threads = 64)
 {
-    int dev = 0, cus = 256, per = 0;
+    int dev = 0, per = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     if (const int c = cache[dev].load(std::memory_order_relaxed)) return c;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, threads, 0) != hipSuccess || per <= 0) per = 8;
-    cache[dev].store(per * cus, std::memory_order_relaxed);
-    return per * cus;
+    const int res = per * device_cus();
+    cache[dev].store(res, std::memory_order_relaxed);
+    return res;
 }
 
 // Balanced static schedule: the fewest items per wave that fit the resident waves, then only as

@@ -11,7 +11,7 @@ namespace sde {
 // straight into padded 272-B LDS rows, without passing through VGPRs.  A buffer descriptor per
 // feature row makes out-of-image rows load zeros (cd_desc); one wave-instruction moves 1 KiB
 // (cd_dma16); a unit is 32 padded rows = 8.5 instructions, lane s loading chunk s % 17 of row
-// s / 17, chunk 16 being the pad (c3_unit); cd_rsrc is the descriptor of the volume
+// s / 17, chunk 16 being the pad (c3_unit); buf_rsrc is the descriptor of the volume
 // stores, whose out-of-image rows are dropped by the range check; cd_barrier waits for the LDS
 // counter only, so DMA and stores stay in flight across the barrier.
 // ---------------------------------------------------------------------------
@@ -45,16 +45,6 @@ __device__ __forceinline__ void cd_dma16(cd_u32x4 rs, uint32_t voff, uint32_t ld
                  : "=&s"(keep)
                  : "v"(voff), "s"(rs), "s"(lds_dst)
                  : "memory");
-}
-
-constexpr uint32_t CD_OOB = 0x80000000u;                 // past any row's records
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t cd_rsrc(const void *base, uint32_t bytes)
-{
-    const uintptr_t b = (uintptr_t)base;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)hi << 32) | lo), 0,
-                                             (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 
 __device__ __forceinline__ void cd_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -143,9 +133,9 @@ __global__ __launch_bounds__(256, 2) void cvlr3_kernel(const float *__restrict__
     const size_t rowvox = (size_t)y * W;
     const cd_u32x4 rs_o = cd_desc(fl + rowvox * 64, (uint32_t)W * 256u);   // own pixels' feature row
     const cd_u32x4 rs_r = cd_desc(fr + rowvox * 64, (uint32_t)W * 256u);   // other side's
-    // row y of each volume (the host guarantees 4 W D < CD_OOB)
-    const __amdgpu_buffer_rsrc_t rl = cd_rsrc(outl + rowvox * D, (uint32_t)W * D * 4u);
-    const __amdgpu_buffer_rsrc_t rr = cd_rsrc(WR ? outr + rowvox * D : outl, (uint32_t)W * D * 4u);
+    // row y of each volume (the host guarantees 4 W D < BUF_OOB)
+    const __amdgpu_buffer_rsrc_t rl = buf_rsrc(outl + rowvox * D, (uint32_t)W * D * 4u);
+    const __amdgpu_buffer_rsrc_t rr = buf_rsrc(WR ? outr + rowvox * D : outl, (uint32_t)W * D * 4u);
     // strips: the emission after strip k completes R rows [q0-dc-63, q0-dc] (whatever nd), so
     // the last strip holds x = W-1+dc+63 (left volume only: the last strip holds x = W-1)
     const int nstrips = WR ? (W + dc + 62) / C3_NX + 1 : (W + C3_NX - 1) / C3_NX;
@@ -171,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void cvlr3_kernel(const float *__restrict__
     for (int n = 0; n < 16; n++) cr[n] = invalid;
     const float *tl = T + lane * C3_TS + wave;
     const float *tr = T + lane * (C3_TS + 1) + wave - 63;
-    const uint32_t voff_d = lane < nd ? 4u * lane : CD_OOB;
+    const uint32_t voff_d = lane < nd ? 4u * lane : BUF_OOB;
     auto emit_load = [&]() {
 #pragma unroll
         for (int n = 0; n < 16; n++) {
@@ -182,8 +172,8 @@ __global__ __launch_bounds__(256, 2) void cvlr3_kernel(const float *__restrict__
         }
     };
     // stores 8j .. 8j+7 of the 32 (16 L, 16 R runs), issued in the first four dot rows so they
-    // drain while the strip computes.  A row outside the image stores with voffset CD_OOB: the
-    // buffer range check compares the voffset with the records (4 W D < CD_OOB) and drops it, with
+    // drain while the strip computes.  A row outside the image stores with voffset BUF_OOB: the
+    // buffer range check compares the voffset with the records (4 W D < BUF_OOB) and drops it, with
     // or without the soffset counted in (row offsets < 2^31: the sum cannot wrap) -- one select per
     // store, no branch.
     auto emit_store = [&](int qp, int j) {
@@ -194,13 +184,13 @@ __global__ __launch_bounds__(256, 2) void cvlr3_kernel(const float *__restrict__
                 const int x = qp + wave + 4 * n;
                 const bool in = x < W;
                 const uint32_t so = in ? (uint32_t)(((qp + wave) * D + dc) * 4 + n * rowstep) : 0u;
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, vl[n]), rl, in ? voff_d : CD_OOB, so,
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, vl[n]), rl, in ? voff_d : BUF_OOB, so,
                                                       C3_AUX);
             } else {
                 const int xr = qp - dc - 63 + 4 * (n - 16) + wave;
                 const bool in = (uint32_t)xr < (uint32_t)W;
                 const uint32_t so = in ? (uint32_t)(((qp - dc - 63 + wave) * D + dc) * 4 + (n - 16) * rowstep) : 0u;
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, vr[n - 16]), rr, in ? voff_d : CD_OOB,
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, vr[n - 16]), rr, in ? voff_d : BUF_OOB,
                                                       so, C3_AUX);
             }
         }

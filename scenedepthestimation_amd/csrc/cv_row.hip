@@ -522,30 +522,20 @@ void launch_row_cert(const float *fl, const float *fr, int H, int W, int d0, int
                      float *out_disp, unsigned *counter, int32_t *list, hipStream_t st, const float *prev_min,
                      bool mirror)
 {
-    static std::atomic<uint64_t> attr{0};
-    once_per_device(attr, [] {
-        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<true, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<false, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<true, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        (void)hipFuncSetAttribute((const void *)cv_wta_row2_kernel<false, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    });
+    constexpr size_t MAX = 150 * 1024;
     const RowWindow w = row_window(d0, d1);
     if (out_min && mirror)
-        cv_wta_row2_kernel<true, true><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, out_min,
-                                                                out_arg, out_disp, counter, list, prev_min);
+        launch_lds_dyn<cv_wta_row2_kernel<true, true>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt,
+                                                            out_min, out_arg, out_disp, counter, list, prev_min);
     else if (out_min)
-        cv_wta_row2_kernel<true, false><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, out_min,
-                                                                 out_arg, out_disp, counter, list, prev_min);
+        launch_lds_dyn<cv_wta_row2_kernel<true, false>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt,
+                                                             out_min, out_arg, out_disp, counter, list, prev_min);
     else if (mirror)
-        cv_wta_row2_kernel<false, true><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, nullptr,
-                                                                 out_arg, out_disp, counter, list, nullptr);
+        launch_lds_dyn<cv_wta_row2_kernel<false, true>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt,
+                                                             nullptr, out_arg, out_disp, counter, list, nullptr);
     else
-        cv_wta_row2_kernel<false, false><<<H, 512, w.smem, st>>>(fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt, nullptr,
-                                                                  out_arg, out_disp, counter, list, nullptr);
+        launch_lds_dyn<cv_wta_row2_kernel<false, false>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt,
+                                                              nullptr, out_arg, out_disp, counter, list, nullptr);
 }
 
 }  // namespace sde

@@ -20,7 +20,7 @@ SDE_EXPORT int sde_cost_volume(const float *fl, const float *fr, int H, int W, i
         if (layout == SDE_LAYOUT_DHW) {
             cv64_kernel<SDE_SIDE_LEFT, OUT_DHW><<<grid, 256, 0, st>>>(fl, fr, H, W, 0, D, D, invalid, out_left,
                                                                        nullptr, nullptr, nullptr);
-        } else if ((int64_t)W * D * 4 < (int64_t)CD_OOB) {
+        } else if ((int64_t)W * D * 4 < (int64_t)BUF_OOB) {
             // one row sweep per (row, 64-disparity chunk) writes both volumes (the left one alone: the
             // same sweep without the right volume's stores).  (Rows of 2 GiB or more take the per-side
             // kernels below.)  A failed >64 KB dynamic-LDS opt-in surfaces as the failed launch:

@@ -118,8 +118,6 @@ __global__ __launch_bounds__(256) void remap_u8_kernel(const uint8_t *__restrict
     }
 }
 
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7fffffffu) < 0x7f800000u; }
-
 __global__ __launch_bounds__(256) void reproject_kernel(const float *__restrict__ disp, int W, int npix, GeomQ Q,
                                                         float min_disp, float *__restrict__ depth,
                                                         float *__restrict__ xyz)

@@ -387,13 +387,7 @@ SDE_EXPORT int sde_ad_wta(const uint8_t *img_l, const uint8_t *img_r, int H, int
         ad_wta_kernel<4><<<grid, AW_THREADS, smem, st>>>(img_l, img_r, H, W, D, radius, rpitch, disp, min_cost);
         return launch_status();
     }
-    if (smem > 64 * 1024) {
-        static std::atomic<uint64_t> attr{0};
-        once_per_device(attr, [] {
-            (void)hipFuncSetAttribute((const void *)ad_wta_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      AW_MAX_SMEM);
-        });
-    }
-    ad_wta_kernel<8><<<grid, AW_THREADS, smem, st>>>(img_l, img_r, H, W, D, radius, rpitch, disp, min_cost);
+    launch_lds_dyn<ad_wta_kernel<8>, AW_MAX_SMEM>(grid, AW_THREADS, smem, st, img_l, img_r, H, W, D, radius, rpitch, disp,
+                                                  min_cost);
     return launch_status();
 }

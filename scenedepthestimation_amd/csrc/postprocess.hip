@@ -104,6 +104,20 @@ __device__ __forceinline__ int wave_max_scan(int v)
     return v;
 }
 
+// One 64-position chunk of a sweep.  mine: this lane's index along the sweep if its pixel is unflagged, else
+// -1; carry: the largest unflagged index of the chunks before (-1 = none).  Returns the nearest unflagged
+// index strictly before this lane (-1 = none) and advances carry past the chunk.
+__device__ __forceinline__ int lrc_nearest_before(int mine, int &carry)
+{
+    const int v = wave_max_scan(mine);
+    int prev = __shfl_up(v, 1, 64);
+    if ((threadIdx.x & 63) == 0) prev = -1;
+    const int near = prev > carry ? prev : carry;
+    const int last = __builtin_amdgcn_readlane(v, 63);
+    carry = last > carry ? last : carry;
+    return near;
+}
+
 // Pass 1: one wave per column, 64 rows per step, wave-wide max-scans downwards (nearest
 // unflagged row above, strictly) and upwards (below), carried across chunks.
 __global__ __launch_bounds__(64) void lrc_cols_kernel(const uint8_t *__restrict__ f, int H, int W,
@@ -117,12 +131,7 @@ __global__ __launch_bounds__(64) void lrc_cols_kernel(const uint8_t *__restrict_
         const int y = c * 64 + lane;
         const bool in = y < H;
         const bool flagged = in && f[(size_t)y * W + x] == 1;
-        const int v = wave_max_scan(in && !flagged ? y : -1);
-        int prev = __shfl_up(v, 1, 64);
-        if (lane == 0) prev = -1;
-        const int up = prev > carry ? prev : carry;
-        const int last = __builtin_amdgcn_readlane(v, 63);
-        carry = last > carry ? last : carry;
+        const int up = lrc_nearest_before(in && !flagged ? y : -1, carry);
         if (flagged) park[(size_t)y * W + x] = up < 0 ? LRC_NONE : (uint32_t)up;
     }
     carry = -1;                                    // as H-1-y of the nearest unflagged row below
@@ -130,12 +139,7 @@ __global__ __launch_bounds__(64) void lrc_cols_kernel(const uint8_t *__restrict_
         const int y = H - 1 - (c * 64 + lane);
         const bool in = y >= 0;
         const bool flagged = in && f[(size_t)(in ? y : 0) * W + x] == 1;
-        const int v = wave_max_scan(in && !flagged ? H - 1 - y : -1);
-        int prev = __shfl_up(v, 1, 64);
-        if (lane == 0) prev = -1;
-        const int dn = prev > carry ? prev : carry;
-        const int last = __builtin_amdgcn_readlane(v, 63);
-        carry = last > carry ? last : carry;
+        const int dn = lrc_nearest_before(in && !flagged ? H - 1 - y : -1, carry);
         if (flagged) park[(size_t)y * W + x] |= (dn < 0 ? LRC_NONE : (uint32_t)(H - 1 - dn)) << 16;
     }
 }
@@ -155,6 +159,7 @@ __global__ __launch_bounds__(64) void lrc_rows_kernel(const float *__restrict__ 
         const int x = c * 64 + lane;
         const bool in = x < W;
         const bool clear = in && f[row + x] != 1;
+        // lrc_nearest_before's step written out: here the store sits before the carry's readlane
         const int v = wave_max_scan(clear ? x : -1);
         int prev = __shfl_up(v, 1, 64);
         if (lane == 0) prev = -1;
@@ -169,12 +174,7 @@ __global__ __launch_bounds__(64) void lrc_rows_kernel(const float *__restrict__ 
         const int x = W - 1 - (c * 64 + lane);
         const bool in = x >= 0;
         const bool flagged = in && f[row + x] == 1;
-        const int v = wave_max_scan(in && !flagged ? W - 1 - x : -1);
-        int prev = __shfl_up(v, 1, 64);
-        if (lane == 0) prev = -1;
-        const int rr = prev > carry ? prev : carry;
-        const int last = __builtin_amdgcn_readlane(v, 63);
-        carry = last > carry ? last : carry;
+        const int rr = lrc_nearest_before(in && !flagged ? W - 1 - x : -1, carry);
         if (!in) continue;
         if (!flagged) {
             out[row + x] = dl[row + x];
@@ -243,16 +243,8 @@ SDE_EXPORT int sde_lrc_fill(const float *disp_l, const uint8_t *lrc_l, int H, in
     // 16-bit row / column indices (0xFFFF = none); the row pass keeps 2 B per column in LDS (<= 128 KB)
     if (H >= (int)LRC_NONE || W >= (int)LRC_NONE || out == disp_l) return SDE_ERR_ARG;
     hipStream_t st = as_stream(stream);
-    const size_t smem = 2 * (size_t)W;
-    if (smem > 64 * 1024) {
-        static std::atomic<uint64_t> attr{0};
-        once_per_device(attr, [] {
-            (void)hipFuncSetAttribute((const void *)lrc_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      2 * (int)LRC_NONE);
-        });
-    }
     lrc_cols_kernel<<<W, 64, 0, st>>>(lrc_l, H, W, reinterpret_cast<uint32_t *>(out));
-    lrc_rows_kernel<<<H, 64, smem, st>>>(disp_l, lrc_l, H, W, out);
+    launch_lds_dyn<lrc_rows_kernel, 2 * LRC_NONE>(H, 64, 2 * (size_t)W, st, disp_l, lrc_l, H, W, out);
     return launch_status();
 }
 

@@ -1,99 +1,16 @@
-// refine.hip -- sub-pixel disparities and the 9x9 bilateral filter (gfx950): sde_wta_subpixel, sde_cv_subpixel,
-// sde_bilateral9.
+// refine.hip -- sub-pixel disparities from the features and the 9x9 bilateral filter (gfx950): sde_cv_subpixel,
+// sde_bilateral9.  (Sub-pixel WTA over a stored volume, sde_wta_subpixel, is wta.hip's.)
 //
 // Replaces (process_functional.py), both switched off in the reference:
-//   the parabola step of WTA_and_SupixelRefinement_kernel :813-819 / :830-836
+//   the parabola step of WTA_and_SupixelRefinement_kernel :813-819 / :830-836 (subpixel.h), here on the exact
+//                                                         costs recomputed around a given integer winner
 //   Bilateral_Filter_kernel                               :882-974 (call commented out at :1260)
 //
 // Numerics are stated in include/sde.h down to the rounding.  The library is built with -ffp-contract=off, so
 // every operation below is rounded on its own.
-#include "sde_common.h"
+#include "subpixel.h"
 
 namespace sde {
-
-__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7fffffffu) < 0x7f800000u; }
-
-// Numba's promotion of `index - (c_ - _c)/(2*(_c + c_ - 2*c))` (:818): the difference and the sum of the two
-// neighbours are float32, `2*c` is int64 * float32 = float64 and everything after it is float64.  The three
-// guards (an interior winner, finite costs, a convex parabola) keep the integer; there is no clamp.
-__device__ __forceinline__ float refine(int i, int lo, int hi, float cm, float c0, float cp)
-{
-    float r = (float)i;
-    if (i > lo && i < hi - 1 && finite_f32(cm) && finite_f32(c0) && finite_f32(cp)) {
-        const float num = cp - cm;
-        const float s = cm + cp;
-        const double den = 2.0 * ((double)s - 2.0 * (double)c0);
-        if (den > 0.0) r = (float)((double)i - (double)num / den);
-    }
-    return r;
-}
-
-// [D][H][W]: wta_dhw_kernel's scan (one lane per pixel, every d-slice coalesced along W), then the winner's
-// two neighbours re-read from the slices the scan has just pulled through the cache.
-template <int RULE>
-__global__ __launch_bounds__(256) void wta_subpixel_dhw_kernel(const float *__restrict__ vol, int64_t npix, int D,
-                                                               float *__restrict__ disp)
-{
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= npix) return;
-    float best;
-    int arg;
-    if (RULE == SDE_WTA_INIT_D0) { best = vol[p]; arg = 0; }
-    else { best = __builtin_inff(); arg = -1; }
-    for (int d = (RULE == SDE_WTA_INIT_D0 ? 1 : 0); d < D; d++) {
-        const float v = vol[(size_t)d * npix + p];
-        if (v < best) { best = v; arg = d; }
-    }
-    float r = (float)arg;
-    if (arg > 0 && arg < D - 1) {
-        const float cm = vol[(size_t)(arg - 1) * npix + p];
-        const float c0 = vol[(size_t)arg * npix + p];
-        const float cp = vol[(size_t)(arg + 1) * npix + p];
-        r = refine(arg, 0, D, cm, c0, cp);
-    }
-    disp[p] = r;
-}
-
-// [H][W][D]: wta_hwd_kernel's mapping (16 lanes per pixel, strided scans, a (value, index) butterfly that leaves
-// the winner in all 16 lanes).  Lanes 0..2 of the pixel then load the costs at winner - 1, winner, winner + 1 in
-// one instruction -- the pixel's row is in the cache from the scan -- and lane 0 collects them across lanes.
-template <int RULE>
-__global__ __launch_bounds__(256) void wta_subpixel_hwd_kernel(const float *__restrict__ vol, int64_t npix, int D,
-                                                               float *__restrict__ disp)
-{
-    const int lane = threadIdx.x & 63;
-    const int sub = threadIdx.x & 15;
-    const int64_t p = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-    const bool ok = p < npix;
-    const float *v = vol + (size_t)(ok ? p : 0) * D;
-    float best = __builtin_inff();
-    int arg = -1;
-    if (ok) {
-        for (int d = sub; d < D; d += 16) {
-            const float x = v[d];
-            if (x < best) { best = x; arg = d; }
-        }
-    }
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) {
-        const float ob = __shfl_xor(best, off, 64);
-        const int oa = __shfl_xor(arg, off, 64);
-        argmin_merge(best, arg, ob, oa);
-    }
-    if (RULE == SDE_WTA_INIT_D0) {
-        // as wta_hwd_kernel: "no winner" reads 0 and a NaN at d = 0 is never replaced
-        const float v0 = v[0];
-        if (arg < 0 || v0 != v0) arg = 0;
-    }
-    const bool inner = ok && arg > 0 && arg < D - 1;
-    float c = 0.0f;
-    if (inner && sub < 3) c = v[arg - 1 + sub];
-    const int base = lane & ~15;
-    const float cm = __shfl(c, base, 64);
-    const float c0 = __shfl(c, base + 1, 64);
-    const float cp = __shfl(c, base + 2, 64);
-    if (ok && sub == 0) disp[p] = inner ? refine(arg, 0, D, cm, c0, cp) : (float)arg;
-}
 
 // The value sde_cost_volume(..., SDE_LAYOUT_DHW) holds at disparity d for the own pixel (row `own`, column x of
 // its view): left view cost(x, d) with the other pixel at x - d, right view cost(x + d, d) with the other pixel at
@@ -256,26 +173,6 @@ __global__ __launch_bounds__(256) void bilateral9_kernel(const uint8_t *__restri
 }  // namespace sde
 
 using namespace sde;
-
-SDE_EXPORT int sde_wta_subpixel(const float *vol, int H, int W, int D, int layout, int rule, float *disp, void *stream)
-{
-    if (!vol || !disp || H <= 0 || W <= 0 || D <= 0) return SDE_ERR_ARG;
-    if (rule != SDE_WTA_INIT_INF && rule != SDE_WTA_INIT_D0) return SDE_ERR_ARG;
-    hipStream_t st = as_stream(stream);
-    const int64_t npix = (int64_t)H * W;
-    if (layout == SDE_LAYOUT_DHW) {
-        const int blocks = cdiv(npix, 256);
-        if (rule == SDE_WTA_INIT_INF) wta_subpixel_dhw_kernel<SDE_WTA_INIT_INF><<<blocks, 256, 0, st>>>(vol, npix, D, disp);
-        else wta_subpixel_dhw_kernel<SDE_WTA_INIT_D0><<<blocks, 256, 0, st>>>(vol, npix, D, disp);
-    } else if (layout == SDE_LAYOUT_HWD) {
-        const int blocks = cdiv(npix * 16, 256);
-        if (rule == SDE_WTA_INIT_INF) wta_subpixel_hwd_kernel<SDE_WTA_INIT_INF><<<blocks, 256, 0, st>>>(vol, npix, D, disp);
-        else wta_subpixel_hwd_kernel<SDE_WTA_INIT_D0><<<blocks, 256, 0, st>>>(vol, npix, D, disp);
-    } else {
-        return SDE_ERR_ARG;
-    }
-    return launch_status();
-}
 
 SDE_EXPORT int sde_cv_subpixel(const float *fl, const float *fr, int H, int W, int C, int d0, int d1, int side,
                                const float *disp_in, float *disp_out, void *stream)

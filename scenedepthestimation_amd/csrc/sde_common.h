@@ -47,18 +47,53 @@ static inline bool once_per_device(std::atomic<uint64_t> &done, F fn)
     return ok;
 }
 
-// Launch kernel K with SMEM bytes of dynamic LDS.  More than 64 KB needs a per-device opt-in on the kernel:
-// it is made here, on K's first launch on a device, so no instantiation can be launched without it.  (The
-// function-local atomic is trivially destructible: no exit-time code.)
-template <auto K, size_t SMEM, typename... Args>
-static inline void launch_lds(dim3 grid, dim3 block, hipStream_t st, Args... args)
+// Launch kernel K with smem <= MAX bytes of dynamic LDS.  More than 64 KB needs a per-device opt-in on the
+// kernel: it is made here (for MAX bytes), on K's first launch on a device whatever that launch's size, so no
+// instantiation can be launched without it.  (The function-local atomic is trivially destructible: no
+// exit-time code.)
+template <auto K, size_t MAX, typename... Args>
+static inline void launch_lds_dyn(dim3 grid, dim3 block, size_t smem, hipStream_t st, Args... args)
 {
     static std::atomic<uint64_t> done{0};
     once_per_device(done, [] {
-        (void)hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM);
+        (void)hipFuncSetAttribute((const void *)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MAX);
     });
-    hipLaunchKernelGGL(K, grid, block, SMEM, st, args...);
+    hipLaunchKernelGGL(K, grid, block, smem, st, args...);
 }
+
+// ... with a compile-time size
+template <auto K, size_t SMEM, typename... Args>
+static inline void launch_lds(dim3 grid, dim3 block, hipStream_t st, Args... args)
+{
+    launch_lds_dyn<K, SMEM>(grid, block, SMEM, st, args...);
+}
+
+// CU count of the current device, cached per device id (256 when the runtime does not say).
+static inline int device_cus()
+{
+    static std::atomic<int> cached[64];
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    if (const int c = cached[dev].load(std::memory_order_relaxed)) return c;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cached[dev].store(n, std::memory_order_relaxed);
+    return n;
+}
+
+// Buffer descriptor (wave-uniform inputs only) for raw buffer loads/stores with a 32-bit per-lane voffset, an
+// SGPR soffset and the hardware range check on voffset (>= bytes: load 0, store dropped).  Every range in
+// use is < 2^31, so a voffset of BUF_OOB is out of every range: no exec-mask branch around an edge lane.
+constexpr uint32_t BUF_OOB = 0x80000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void *base, uint32_t bytes)
+{
+    const uintptr_t b = (uintptr_t)base;
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)hi << 32) | lo), 0,
+                                             (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+
+__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7fffffffu) < 0x7f800000u; }
 
 // Logical id of block b of nb, so that the blocks one XCD runs share its L2 on neighbouring work.
 __device__ __forceinline__ int xcd_remap(int b, int nb)

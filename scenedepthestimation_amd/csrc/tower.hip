@@ -97,16 +97,9 @@ static std::atomic<int> g_grid_cus{0};
 
 static int cu_count()
 {
-    static int cached[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (!cached[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cached[dev] = n;
-    }
+    const int cus = device_cus();
     const int g = g_grid_cus.load(std::memory_order_relaxed);
-    return g > 0 ? std::min(g, cached[dev]) : cached[dev];
+    return g > 0 ? std::min(g, cus) : cus;
 }
 
 // The tile space of a batch launch (tw x th output tiles, image-major) and the persistent grid that walks it

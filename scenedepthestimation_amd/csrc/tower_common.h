@@ -93,20 +93,11 @@ __device__ __forceinline__ void xp_publish_scale(bool first, const XpBatch &bt, 
 }
 
 // Epilogue stores: buffer descriptors on a per-tile base (wave-uniform), 32-bit per-lane byte
-// offsets with an SGPR row offset; a lane outside the output (x >= Wout) gets XP_OOB, which the
+// offsets with an SGPR row offset; a lane outside the output (x >= Wout) gets BUF_OOB, which the
 // descriptor's range check drops -- no exec-mask branches, no 64-bit address math per store.
-constexpr uint32_t XP_NREC = 0x40000000u, XP_OOB = 0x80000000u;
-
-// a descriptor with nrec bytes of records (loads past them return zero)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t xp_rsrc_n(const void *base, uint32_t nrec)
-{
-    const uintptr_t b = (uintptr_t)base;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)(((uintptr_t)hi << 32) | lo), 0,
-                                             (int)__builtin_amdgcn_readfirstlane(nrec), 0x00020000);
-}
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t xp_rsrc(const void *base) { return xp_rsrc_n(base, XP_NREC); }
+// (Descriptors with an exact record count, whose loads past it return zero: buf_rsrc(base, nrec).)
+constexpr uint32_t XP_NREC = 0x40000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t xp_rsrc(const void *base) { return buf_rsrc(base, XP_NREC); }
 
 __device__ __forceinline__ void xp_st4(float4 v, __amdgpu_buffer_rsrc_t r, uint32_t vo, uint32_t so)
 {

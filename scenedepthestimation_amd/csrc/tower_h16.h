@@ -127,7 +127,7 @@ __device__ __forceinline__ void h16_stager_loop(char *hsm, const float *__restri
         const int u = h16_unit(st, i), px = u >> 2, chunk = u & 3;
         const int iy = px / T::IX, ix = px - iy * T::IX;
         const bool ok = u < T::UNITS;
-        uoff[i] = ok ? (uint32_t)((iy * Win + ix) * (IN_CB ? 64 : 256) + 16 * chunk) : XP_OOB;
+        uoff[i] = ok ? (uint32_t)((iy * Win + ix) * (IN_CB ? 64 : 256) + 16 * chunk) : BUF_OOB;
         uyx[i] = ok ? (uint32_t)(iy << 16 | ix) : 0xFFFF0000u;
         ulds[i] = ok ? (uint32_t)((chunk >> 1) * T::PLANE + px * 16 + (chunk & 1) * 8) : 0u;
     }
@@ -148,7 +148,7 @@ __device__ __forceinline__ void h16_stager_loop(char *hsm, const float *__restri
 #pragma unroll
             for (int i = 0; i < T::UPT; i++) {
                 const bool ok = (int)(uyx[i] >> 16) < ly && (int)(uyx[i] & 0xFFFFu) < lx;
-                v[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? uoff[i] : XP_OOB, 0, H16_ACT_AUX));
+                v[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, ok ? uoff[i] : BUF_OOB, 0, H16_ACT_AUX));
             }
         }
     };
@@ -329,7 +329,7 @@ __device__ __forceinline__ void h16_dma_stager_loop(char *hsm, const float *__re
 #pragma unroll
         for (int pp = 0; pp < 2; pp++) {
             const int p = 2 * w + pp;
-            const __amdgpu_buffer_rsrc_t rs = xp_rsrc_n(src + p * PB, (uint32_t)(PB - org));
+            const __amdgpu_buffer_rsrc_t rs = buf_rsrc(src + p * PB, (uint32_t)(PB - org));
             auto *lds = (__attribute__((address_space(3))) char *)(dst + p * H16_PLANE);
 #pragma unroll
             for (int d = 0; d < ND - 1; d++)
@@ -549,7 +549,7 @@ __device__ __forceinline__ void h16_epilogue(const floatx4 (&acc)[32], int lane,
                                 amax = max(amax, max(__float_as_uint(o.x), __float_as_uint(o.y)));
                                 amax = max(amax, max(__float_as_uint(o.z), __float_as_uint(o.w)));
                             }
-                            const uint32_t v2 = xok ? ospl_lane + (uint32_t)x * 16u : XP_OOB;
+                            const uint32_t v2 = xok ? ospl_lane + (uint32_t)x * 16u : BUF_OOB;
                             const uint32_t s2 = (uint32_t)((row0 + r) * Wout) * 16u;
                             __builtin_amdgcn_raw_buffer_store_b128(v4, rs, v2, s2, 0);
                         }
@@ -560,7 +560,7 @@ __device__ __forceinline__ void h16_epilogue(const floatx4 (&acc)[32], int lane,
                                 amax = max(amax, max(__float_as_uint(o.x), __float_as_uint(o.y)));
                                 amax = max(amax, max(__float_as_uint(o.z), __float_as_uint(o.w)));
                             }
-                            xp_st4(o, rs, xok ? (uint32_t)(OUT_CB ? x * 64 + 16 * k4 : x * 256 + 64 * q + 16 * k4) : XP_OOB, so);
+                            xp_st4(o, rs, xok ? (uint32_t)(OUT_CB ? x * 64 + 16 * k4 : x * 256 + 64 * q + 16 * k4) : BUF_OOB, so);
                         }
                     }
                     asm volatile("s_nop 2" ::"v"(pin[k >= XP_PIN - 1 ? k - (XP_PIN - 1) : k]) : "memory");   // after each store: >= 9 wait states over XP_PIN stores
@@ -613,7 +613,7 @@ __device__ __forceinline__ void h16_epilogue(const floatx4 (&acc)[32], int lane,
                 ss += __shfl_xor(ss, 32, 64);
                 const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
                 const bool xok = FULL || x < Wout;
-                const uint32_t vo = xok ? (uint32_t)(x * 256 + 16 * k4) : XP_OOB;
+                const uint32_t vo = xok ? (uint32_t)(x * 256 + 16 * k4) : BUF_OOB;
                 float s2 = 0.0f;
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
@@ -634,7 +634,7 @@ __device__ __forceinline__ void h16_epilogue(const floatx4 (&acc)[32], int lane,
                         }
                         if (rok) {
                             const __amdgpu_buffer_rsrc_t rh = xp_rsrc(ohi + pix0 * NF), rl = xp_rsrc(olo + pix0 * NF);
-                            const uint32_t o2 = xok ? (uint32_t)(x * 128 + 32 * q + 8 * k4) : XP_OOB;
+                            const uint32_t o2 = xok ? (uint32_t)(x * 128 + 32 * q + 8 * k4) : BUF_OOB;
                             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, hv), rh, o2, so / 2u, 0);
                             __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, lv), rl, o2, so / 2u, 0);
                         }
@@ -646,7 +646,7 @@ __device__ __forceinline__ void h16_epilogue(const floatx4 (&acc)[32], int lane,
                     if (rok) {
                         const __amdgpu_buffer_rsrc_t rn = xp_rsrc(onrm + pix0);
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, sqrtf(s2) * 1.000004f), rn,
-                                                              (xok && k4 == 0) ? (uint32_t)(x * 4) : XP_OOB, so / 64u, 0);
+                                                              (xok && k4 == 0) ? (uint32_t)(x * 4) : BUF_OOB, so / 64u, 0);
                     }
                 }
             }

@@ -43,7 +43,7 @@ __device__ __forceinline__ void h16_dma_issue(char *hsm, const float *__restrict
 #pragma unroll
     for (int pp = 0; pp < 2; pp++) {
         const int p = 2 * w + pp;
-        const __amdgpu_buffer_rsrc_t rs = xp_rsrc_n(src + p * PB, (uint32_t)(PB - org));
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc(src + p * PB, (uint32_t)(PB - org));
         auto *lds = (__attribute__((address_space(3))) char *)(dst + p * H16_PLANE);
 #pragma unroll
         for (int d = 0; d < ND - 1; d++)
@@ -168,7 +168,7 @@ __device__ __forceinline__ void h16q_epilogue(const floatx4 (&acc)[32], int lane
                 xp_split16s(o, hw2, lw2);
                 const int k = r * 2 + ph;
                 pin[k] = xp_pair_parts(hw2, lw2);
-                __builtin_amdgcn_raw_buffer_store_b128(pin[k], rs, ok ? lane_pl + (uint32_t)x * 16u : XP_OOB, so, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(pin[k], rs, ok ? lane_pl + (uint32_t)x * 16u : BUF_OOB, so, 0);
                 if (k >= XP_PIN - 1) asm volatile("" ::"v"(pin[k - (XP_PIN - 1)]));
             }
         }

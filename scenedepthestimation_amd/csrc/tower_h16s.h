@@ -108,7 +108,7 @@ struct H16sOut {
 // [h][w][64] store -- or (LAST) the L2 norm in h16_epilogue's summation tree (per lane the running sum over
 // (q, e), then (p0 + p1) + (p2 + p3)) and the [h][w][64] features.  Stores as there: per-tile descriptors,
 // interior tiles without range selects, stored registers pinned for XP_PIN stores; on edge tiles lanes AND rows
-// outside the image take the offset XP_OOB, so that no store sits behind a branch (the ISA lint reads the
+// outside the image take the offset BUF_OOB, so that no store sits behind a branch (the ISA lint reads the
 // listing linearly: a store that ends a block must not be followed by another block's VALU writes).
 template <class T, bool LAST, bool OUT_CB, typename GET>
 __device__ __forceinline__ void h16s_rows_out(H16sOut &o, GET &&get, int lane, int j, int k4, int R0, int img, int ty0,
@@ -138,7 +138,7 @@ __device__ __forceinline__ void h16s_rows_out(H16sOut &o, GET &&get, int lane, i
                 const float bq[4] = {o.bias[q].x, o.bias[q].y, o.bias[q].z, o.bias[q].w};
                 const __amdgpu_buffer_rsrc_t rs = xp_rsrc(OUT_CB ? outi + ((size_t)q * HW + (size_t)ty0 * Wout) * 16
                                                                  : outi + (size_t)ty0 * Wout * NF);
-                const uint32_t vo = xok ? (uint32_t)(OUT_CB ? x * 64 + 16 * k4 : x * 256 + 64 * q + 16 * k4) : XP_OOB;
+                const uint32_t vo = xok ? (uint32_t)(OUT_CB ? x * 64 + 16 * k4 : x * 256 + 64 * q + 16 * k4) : BUF_OOB;
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const bool rok = FULL || ty0 + R0 + r < Hout;   // wave-uniform
@@ -154,7 +154,7 @@ __device__ __forceinline__ void h16s_rows_out(H16sOut &o, GET &&get, int lane, i
                     const uint32_t m = max(max(__float_as_uint(ov.x), __float_as_uint(ov.y)),
                                            max(__float_as_uint(ov.z), __float_as_uint(ov.w)));
                     amax = max(amax, rok && xok ? m : 0u);
-                    xp_st4(ov, rs, rok ? vo : XP_OOB, so);
+                    xp_st4(ov, rs, rok ? vo : BUF_OOB, so);
                     asm volatile("s_nop 2" ::"v"(pin[k >= XP_PIN - 1 ? k - (XP_PIN - 1) : k]) : "memory");   // after each store: >= 9 wait states over XP_PIN stores
                 }
             }
@@ -176,7 +176,7 @@ __device__ __forceinline__ void h16s_rows_out(H16sOut &o, GET &&get, int lane, i
         auto body = [&](auto fullc) {
             constexpr bool FULL = decltype(fullc)::value;
             const bool xok = FULL || x < Wout;
-            const uint32_t vo = xok ? (uint32_t)(x * 256 + 16 * k4) : XP_OOB;
+            const uint32_t vo = xok ? (uint32_t)(x * 256 + 16 * k4) : BUF_OOB;
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 const bool rok = FULL || ty0 + R0 + r < Hout;
@@ -201,7 +201,7 @@ __device__ __forceinline__ void h16s_rows_out(H16sOut &o, GET &&get, int lane, i
                     const float4 ov = make_float4(t[q][0] * inv, t[q][1] * inv, t[q][2] * inv, t[q][3] * inv);
                     const int k = r * 4 + q;
                     pin[k] = __builtin_bit_cast(u32x4, ov);
-                    xp_st4(ov, rs, rok ? vo + 64u * q : XP_OOB, so);
+                    xp_st4(ov, rs, rok ? vo + 64u * q : BUF_OOB, so);
                     asm volatile("s_nop 2" ::"v"(pin[k >= XP_PIN - 1 ? k - (XP_PIN - 1) : k]) : "memory");   // after each store: >= 9 wait states over XP_PIN stores
                 }
             }

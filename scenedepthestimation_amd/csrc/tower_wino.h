@@ -131,13 +131,13 @@ __device__ __forceinline__ void wn_read_p23(uint32_t pa, wn_f4 (&pr)[4])
 }
 
 // LDS-DMA chunk of wave-instruction ins, lane ln: pixel (chunk >> 2) of the 10 x 18 region,
-// channels 4 (chunk & 3).. -- its byte offset from the region's origin (XP_OOB past the region)
+// channels 4 (chunk & 3).. -- its byte offset from the region's origin (BUF_OOB past the region)
 template <bool IN_CB>
 __device__ __forceinline__ uint32_t wn_loff(int ins, int ln, int Win)
 {
     const int ch = ins * 64 + ln, px = ch >> 2, q = ch & 3;
     const int iy = px / WN_IX, ix = px - iy * WN_IX;
-    return px < WN_IY * WN_IX ? (uint32_t)(iy * Win + ix) * (IN_CB ? 64u : 256u) + 16u * q : XP_OOB;
+    return px < WN_IY * WN_IX ? (uint32_t)(iy * Win + ix) * (IN_CB ? 64u : 256u) + 16u * q : BUF_OOB;
 }
 
 struct WnA {
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
     // resident U fragments: positions 2w + p, M-tile m, c-block cb, parts h / l
     WnA u[2][2][4];
     {
-        const __amdgpu_buffer_rsrc_t ru = xp_rsrc_n(wkblob + LK_WINO, (uint32_t)LK_WU * 2u);
+        const __amdgpu_buffer_rsrc_t ru = buf_rsrc(wkblob + LK_WINO, (uint32_t)LK_WU * 2u);
 #pragma unroll
         for (int p = 0; p < 2; p++)
 #pragma unroll
@@ -201,8 +201,8 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
     };
     auto issue = [&](int g, const float *base, uint32_t bytes) {
         const int cb = g & 3;
-        const __amdgpu_buffer_rsrc_t rs = IN_CB ? xp_rsrc_n(base + (size_t)cb * Hin * Win * 16, bytes)
-                                                : xp_rsrc_n(base + cb * 16, bytes - 64u * cb);
+        const __amdgpu_buffer_rsrc_t rs = IN_CB ? buf_rsrc(base + (size_t)cb * Hin * Win * 16, bytes)
+                                                : buf_rsrc(base + cb * 16, bytes - 64u * cb);
         char *rb = wsm + WN_RAW_OFF + (size_t)(g % WN_RING) * WN_RAW_BYTES;
         int ln = lane;
         asm volatile("" : "+v"(ln));
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
         const int fq = tid_e & 7, fj = (tid_e >> 3) & 1, ft = tid_e >> 4;
         const int oy = ty0 + 2 * (ft >> 3), ox = tx0 + 2 * (ft & 7) + fj;
         const __amdgpu_buffer_rsrc_t orsrc =
-            xp_rsrc_n(LAST ? out + (size_t)img * bt.pix_stride * NF : out + img * bt.out_stride, (uint32_t)Hout * Wout * 256u);
+            buf_rsrc(LAST ? out + (size_t)img * bt.pix_stride * NF : out + img * bt.out_stride, (uint32_t)Hout * Wout * 256u);
         float4 ylast[2][2];
         uint32_t amax = 0u;
 #pragma unroll
@@ -460,7 +460,7 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
                 const uint32_t off = OUT_CB ? (((uint32_t)(c0 >> 4) * Hout + y) * Wout + ox) * 64u + 4u * (c0 & 15)
                                             : ((uint32_t)y * Wout + ox) * 256u + 4u * c0;
                 const u32x4 od = __builtin_bit_cast(u32x4, o);
-                __builtin_amdgcn_raw_buffer_store_b128(od, orsrc, ok ? off : XP_OOB, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b128(od, orsrc, ok ? off : BUF_OOB, 0, 0);
                 // the store's data registers stay untouched for >= 9 wait states ("store-data
                 // overwrite"; _isa_lint.MFMA_STORE_DATA_WINDOW)
                 asm volatile("s_nop 7\n\ts_nop 1" ::"v"(od));
@@ -479,7 +479,7 @@ __global__ __launch_bounds__(512) void wino_kernel(const float *__restrict__ in,
                 ss += __shfl_xor(ss, 4, 64);
                 const float inv = 1.0f / sqrtf(fmaxf(ss, 1e-12f));
                 const int y = oy + i;
-                const uint32_t off = y < Hout && ox < Wout ? ((uint32_t)y * Wout + ox) * 256u + 16u * fq : XP_OOB;
+                const uint32_t off = y < Hout && ox < Wout ? ((uint32_t)y * Wout + ox) * 256u + 16u * fq : BUF_OOB;
                 const u32x4 oa = __builtin_bit_cast(u32x4, make_float4(a.x * inv, a.y * inv, a.z * inv, a.w * inv));
                 const u32x4 ob = __builtin_bit_cast(u32x4, make_float4(b.x * inv, b.y * inv, b.z * inv, b.w * inv));
                 __builtin_amdgcn_raw_buffer_store_b128(oa, orsrc, off, 0, 0);

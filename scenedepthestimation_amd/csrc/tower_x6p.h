@@ -434,7 +434,7 @@ __device__ __forceinline__ void xp_epilogue(const floatx16 (&acc)[XP_ACC], int l
         float *const outi = out + img * bt.out_stride;
         // OUT_CB: [cblk][h][w][16] -> one descriptor per c-block plane, at the tile's first row;
         // else [h][w][64]
-        const uint32_t vo = xok ? (uint32_t)(x * (OUT_CB ? 64 : 256) + 16 * h) : XP_OOB;
+        const uint32_t vo = xok ? (uint32_t)(x * (OUT_CB ? 64 : 256) + 16 * h) : BUF_OOB;
         const size_t HW = (size_t)Hout * Wout;
         // Store-data registers stay untouched for XP_PIN stores ("store-data overwrite"):
         // each stored float4 is pinned live by an empty asm placed after the store XP_PIN - 1 stores
@@ -501,7 +501,7 @@ __device__ __forceinline__ void xp_epilogue(const floatx16 (&acc)[XP_ACC], int l
         // Outputs [h][w][64] (+ bf16 planes, norm bound), descriptors at the tile's first row.
         const size_t pix0 = (size_t)img * bt.pix_stride + (size_t)ty0 * Wout;
         const __amdgpu_buffer_rsrc_t rs = xp_rsrc(out + pix0 * NF);
-        const uint32_t vo = xok ? (uint32_t)(x * 256 + 16 * h) : XP_OOB;
+        const uint32_t vo = xok ? (uint32_t)(x * 256 + 16 * h) : BUF_OOB;
 #pragma unroll
         for (int r = 0; r < XP_WROWS; r++) {
             // biased value of channel m*32 + 8q + 4h + e (bias re-read from LDS per use: nothing
@@ -555,7 +555,7 @@ __device__ __forceinline__ void xp_epilogue(const floatx16 (&acc)[XP_ACC], int l
                                rs, vo + 4u * (m * 32 + 8 * q), rowp * 256u);
                 if (ohi) {
                     const __amdgpu_buffer_rsrc_t rh = xp_rsrc(ohi + pix0 * NF), rl = xp_rsrc(olo + pix0 * NF);
-                    const uint32_t vo2 = xok ? (uint32_t)(x * 128 + 8 * h) : XP_OOB;
+                    const uint32_t vo2 = xok ? (uint32_t)(x * 128 + 8 * h) : BUF_OOB;
 #pragma unroll
                     for (int m = 0; m < 2; m++)
 #pragma unroll
@@ -577,7 +577,7 @@ __device__ __forceinline__ void xp_epilogue(const floatx16 (&acc)[XP_ACC], int l
                 if (onrm) {
                     const __amdgpu_buffer_rsrc_t rn = xp_rsrc(onrm + pix0);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, sqrtf(s2) * 1.000004f), rn,
-                                                          (xok && h == 0) ? (uint32_t)(x * 4) : XP_OOB, rowp * 4u, 0);
+                                                          (xok && h == 0) ? (uint32_t)(x * 4) : BUF_OOB, rowp * 4u, 0);
                 }
             }
         }

@@ -583,6 +583,7 @@ def sgm_direction(cv_hwd, pen, direction: int, S):
 # Cross-based cost aggregation (build-defined; the reference has none)
 # ----------------------------------------------------------------------------
 CBCA_MAX_L1 = 32
+SIDES = {"left": SDE_SIDE_LEFT, "right": SDE_SIDE_RIGHT}
 
 
 def cbca_arms(img, L1=14, tau=0.02, out=None):
@@ -620,7 +621,7 @@ def cbca(cv_hwd, arms_ref, arms_other, side="left", L1=14, iters=2, tmp=None, wo
     if tmp is None:
         tmp = torch.empty_like(cv_hwd)
     ws, nws = _cbca_ws(workspace, H, W, cv_hwd)
-    sd = {"left": SDE_SIDE_LEFT, "right": SDE_SIDE_RIGHT}[side]
+    sd = SIDES[side]
     check(lib.sde_cbca(_need(cv_hwd, "cost volume"), _need(tmp, "tmp", shape=(H, W, D)),
                        _need(arms_ref, "arms_ref", dtype=torch.int32, shape=(H, W)),
                        _need(arms_other, "arms_other", dtype=torch.int32, shape=(H, W)), H, W, D, sd, int(L1),
@@ -713,9 +714,6 @@ def median5(src, dst):
 # Sub-pixel disparities and the 9x9 bilateral filter (process_functional.py:813-819, :882-974; both switched off in
 # the reference; definitions in include/sde.h)
 # ----------------------------------------------------------------------------
-SIDES = {"left": SDE_SIDE_LEFT, "right": SDE_SIDE_RIGHT}
-
-
 def wta_subpixel(vol, layout: str = "DHW", rule: str = "inf", out=None):
     """wta(vol, layout, rule) followed by the parabola step on the winner's two neighbours in the stored volume
     (sde_wta_subpixel): a winner at d = 0 or D - 1, a non-finite neighbour, a parabola that is not convex and a

@@ -1,5 +1,5 @@
 """The sub-pixel step and the 9x9 bilateral filter restated in NumPy scalars and Python floats, independent of the
-kernels (csrc/refine.hip).  include/sde.h states the same three definitions; this file is what the GPU tests compare
+kernels (csrc/wta.hip, refine.hip).  include/sde.h states the same three definitions; this file is what the GPU tests compare
 against, by bytes.
 
     refine         the parabola step of WTA_and_SupixelRefinement_kernel (process_functional.py:813-819), with
