@@ -7,6 +7,7 @@
 // per-score max / median / compare run without NaN canonicalisation, so every
 // decision that must survive non-finite input is taken on integer bit tests.
 #include "cv_cert.h"
+#include "unique.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -179,12 +180,20 @@ __device__ __forceinline__ void r2_store(uint4 *ring, unsigned *tmax, unsigned *
 // rounding) has every cost above the previous chunk's minimum, so this chunk cannot win the in-order merge: it
 // writes (+inf, -1) and skips the certificate and the fix-up.
 // MIRROR: the right view (see the mapping above); fl / fr are the caller's maps in both forms.
-template <bool WANT_MIN, bool MIRROR>
+// UNIQ: the uniqueness check (include/sde_unique.h) decided in the epilogue -- the sweep is the plain one.  Lane (j, h)'s
+// chain tt holds d = dt + j - 4 h - 8 k2 - tt with dt moving by 32 per tile, i.e. one residue class of d modulo 8,
+// (x - 4 h - tt) mod 8: the four chains of lane (j, 0) and the four of lane (j, 1) are the eight classes of pixel x,
+// so the winner i and i - 1, i + 1 sit in three different chains and each chain's best score outside the three is
+// its b2 if its ag is one of them and its b1 otherwise (only the value is used, so ties within a chain are
+// harmless).  s2x, the maximum over the eight, is the fast score of the runner-up of the definition; the decision
+// and its slack are at `eps` below.  prev_min is not used (one sweep only).
+template <bool WANT_MIN, bool MIRROR, bool UNIQ = false>
 __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restrict__ fl, const float *__restrict__ fr,
                                                           int H, int W, int d0, int d1, int tlo0, int nw, int nt,
                                                           float *__restrict__ out_min, int32_t *__restrict__ out_arg,
                                                           float *__restrict__ out_disp, unsigned *__restrict__ counter,
-                                                          int32_t *__restrict__ list, const float *__restrict__ prev_min)
+                                                          int32_t *__restrict__ list, const float *__restrict__ prev_min,
+                                                          float tau, uint8_t *__restrict__ out_rej)
 {
     extern __shared__ __attribute__((aligned(16))) uint4 rsm2[];
     uint4 *ring = rsm2;                                             // [nt][2 planes][32 px][8 chunks]
@@ -255,6 +264,7 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
         const bool xok = x < W;
         float best = -__builtin_inff(), second = -__builtin_inff();
         float wcost = -0.0f;   // WANT_MIN: the winner's exact cost (computed before the barrier)
+        float s2x = -__builtin_inff();   // UNIQ: the best fast score at |d - arg| >= 2
         int arg = -1;
         float nl = 0.0f;
         unsigned nmax2 = 0u, wbad = 0u;
@@ -423,6 +433,18 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                 const int aa = (int)up((uint32_t)arg);
                 fx_merge(best, arg, second, bb, aa, ss2);
             }
+            if constexpr (UNIQ) {
+                // both halves take lane j's merged winner, then their four chains' best score outside its
+                // neighbourhood (ag already holds disparities; an empty chain holds -1 and -inf twice); lanes 0-31
+                // take the maximum over the eight
+                const uint32_t lo_arg = __builtin_amdgcn_permlane32_swap((uint32_t)arg, (uint32_t)arg, false, false)[0];
+                const int ai = h ? (int)lo_arg : arg;
+#pragma unroll
+                for (int t = 0; t < 4; t++)
+                    s2x = fmaxf(s2x, (ag[t] - ai <= 1 && ai - ag[t] <= 1) ? b2[t] : b1[t]);
+                const uint32_t sx = __float_as_uint(s2x);
+                s2x = fmaxf(s2x, __uint_as_float(__builtin_amdgcn_permlane32_swap(sx, sx, false, false)[1]));
+            }
             if constexpr (WANT_MIN) {
                 // the winner's exact cost (used if the pixel certifies), by both lane halves and issued before the
                 // barrier: lane (j, h) forms dot64_exact_global's partial sums acc[4h .. 4h+3] (channels 8m + 4h ..
@@ -476,10 +498,30 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
             // certified only when every operand is finite and no fp16 part can overflow (then every score
             // and eps are finite too)
             const bool fin = !lbad && !wbad && nl < RW_NMAX && nr < RW_NMAX;
+            // UNIQ.  With S = RW_SCALE^2 and c1, c2 the exact costs of the winner and the runner-up, the exact
+            // margin is (c2 - c1) = (s1 - s2) / S over the exact scores; best is within eps of s1 and s2x (a maximum
+            // over the same disparities of scores each within eps) within eps of s2, so Mt = best - s2x is within
+            // 2 eps of S (c2 - c1).  Roundings: Mt and Mt - S tau in fp32 here, 2^-24 (2 Mt + S tau) in all; the
+            // definition's m = fl(c2 - c1) is monotone in c2 - c1 and tau is a float, so m >= tau whenever
+            // c2 - c1 >= tau, and m < tau whenever c2 - c1 <= tau (1 - 2^-23): another 2^-23 S tau.  The sum is
+            // below 2^-22 (Mt + S tau); the slack takes 2^-21.  A pixel is decided here only if its winner
+            // certifies and |Mt - S tau| exceeds 2 eps + slack; s2x = -inf (no d outside the neighbourhood, m =
+            // +inf) and tau = 0 (m >= 0: c1 is the minimum) never reject.
+            bool rej = false, unsure = false;
+            if constexpr (UNIQ) {
+                if (none) {
+                    rej = tau > 0.0f && d1 - d0 >= 3;   // every cost is the fill: m = +0 (+inf below 3 disparities)
+                } else if (tau > 0.0f && s2x != -__builtin_inff()) {
+                    const float st = tau * (RW_SCALE * RW_SCALE), mt = best - s2x;
+                    const float slack = 2.0f * eps + 4.7683716e-7f * (st + mt);   // 2^-21
+                    rej = st - mt > slack;
+                    unsure = !rej && !(mt - st > slack);
+                }
+            }
             if (!none && fin && WANT_MIN && prev_min && best + 2.0f * eps < -prev_min[p] * (RW_SCALE * RW_SCALE)) {
                 out_min[p] = __builtin_inff();
                 if (out_arg) out_arg[p] = -1;
-            } else if (none || (fin && (best - second) > 2.0f * eps && arg >= 0)) {
+            } else if (!(UNIQ && unsure) && (none || (fin && (best - second) > 2.0f * eps && arg >= 0))) {
                 if (none) arg = d0;
                 if (WANT_MIN) {
                     float cost = -0.0f;
@@ -487,7 +529,12 @@ __global__ __launch_bounds__(512) void cv_wta_row2_kernel(const float *__restric
                     out_min[p] = cost;
                 }
                 if (out_arg) out_arg[p] = arg;
-                if (out_disp) out_disp[p] = (float)arg;
+                if constexpr (UNIQ) {
+                    if (out_disp) out_disp[p] = rej ? -1.0f : (float)arg;
+                    if (out_rej) out_rej[p] = rej ? 1 : 0;
+                } else {
+                    if (out_disp) out_disp[p] = (float)arg;
+                }
             } else {
                 // near-ties and non-finite operands: the IEEE fix-up kernel's exact scan
                 list[atomicAdd(counter, 1u)] = (int32_t)p;
@@ -526,16 +573,40 @@ void launch_row_cert(const float *fl, const float *fr, int H, int W, int d0, int
     const RowWindow w = row_window(d0, d1);
     if (out_min && mirror)
         launch_lds_dyn<cv_wta_row2_kernel<true, true>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt,
-                                                            out_min, out_arg, out_disp, counter, list, prev_min);
+                                                            out_min, out_arg, out_disp, counter, list, prev_min, 0.0f, nullptr);
     else if (out_min)
         launch_lds_dyn<cv_wta_row2_kernel<true, false>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt,
-                                                             out_min, out_arg, out_disp, counter, list, prev_min);
+                                                             out_min, out_arg, out_disp, counter, list, prev_min, 0.0f, nullptr);
     else if (mirror)
         launch_lds_dyn<cv_wta_row2_kernel<false, true>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt,
-                                                             nullptr, out_arg, out_disp, counter, list, nullptr);
+                                                             nullptr, out_arg, out_disp, counter, list, nullptr, 0.0f, nullptr);
     else
         launch_lds_dyn<cv_wta_row2_kernel<false, false>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw, w.nt,
-                                                              nullptr, out_arg, out_disp, counter, list, nullptr);
+                                                              nullptr, out_arg, out_disp, counter, list, nullptr, 0.0f, nullptr);
+}
+
+void launch_row_cert_unique(const float *fl, const float *fr, int H, int W, int d0, int d1, float tau, float *out_min,
+                            int32_t *out_arg, float *out_disp, uint8_t *out_rej, unsigned *counter, int32_t *list,
+                            hipStream_t st, bool mirror)
+{
+    constexpr size_t MAX = 150 * 1024;
+    const RowWindow w = row_window(d0, d1);
+    if (out_min && mirror)
+        launch_lds_dyn<cv_wta_row2_kernel<true, true, true>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw,
+                                                                  w.nt, out_min, out_arg, out_disp, counter, list,
+                                                                  nullptr, tau, out_rej);
+    else if (out_min)
+        launch_lds_dyn<cv_wta_row2_kernel<true, false, true>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw,
+                                                                   w.nt, out_min, out_arg, out_disp, counter, list,
+                                                                   nullptr, tau, out_rej);
+    else if (mirror)
+        launch_lds_dyn<cv_wta_row2_kernel<false, true, true>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0, w.nw,
+                                                                   w.nt, nullptr, out_arg, out_disp, counter, list,
+                                                                   nullptr, tau, out_rej);
+    else
+        launch_lds_dyn<cv_wta_row2_kernel<false, false, true>, MAX>(H, 512, w.smem, st, fl, fr, H, W, d0, d1, w.tlo0,
+                                                                    w.nw, w.nt, nullptr, out_arg, out_disp, counter, list,
+                                                                    nullptr, tau, out_rej);
 }
 
 }  // namespace sde

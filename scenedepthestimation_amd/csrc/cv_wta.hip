@@ -3,6 +3,8 @@
 // process_functional.py:48-73 + 96-113, fused.  Exact mode launches cv_exact.h's kernels; certified mode
 // (cv_cert.h) the row sweep of cv_row.hip or the tile path of cv_tile.h, then the exact fix-ups (below).
 #include "cv_tile.h"
+#include "unique.h"
+#include "sde_unique.h"
 
 #include <algorithm>
 
@@ -43,15 +45,21 @@ __global__ __launch_bounds__(256) void argmin_chunks_kernel(const float *__restr
 // RIGHT: the right view's scan -- the listed pixel x owns own[p] = fr[p], the other operand is fl at x + d, valid
 // iff x + d < W (the load index is clamped, as x - d is in the left form); the same per-disparity arithmetic
 // (the products commute) and merge order.  own / other: (fl, fr) for the left view, (fr, fl) for the right.
+// UNIQ: the uniqueness check's resolution (include/sde_unique.h).  A lane's disparities are 8 apart (d = d0 + g modulo 8:
+// Q and the rounds are multiples of 8), one chain of unique.h, taken by all 8 lanes of the group alike; once the
+// winner is merged every lane takes its chain's smallest cost outside the winner's neighbourhood, and the minimum
+// over the groups and the waves is the runner-up: i, c1, c2 and the decision of the exact form, from the same scan.
 constexpr int FX2_U = 8;   // iterations per round of loads
-template <bool RIGHT>
+template <bool RIGHT, bool UNIQ = false>
 __global__ __launch_bounds__(256) void cv_wta_fixup_kernel(const float *__restrict__ own,
                                                            const float *__restrict__ other, int W, int d0, int d1, const unsigned *__restrict__ counter,
                                                            const int32_t *__restrict__ list, float *__restrict__ out_min,
-                                                           int32_t *__restrict__ out_arg, float *__restrict__ out_disp)
+                                                           int32_t *__restrict__ out_arg, float *__restrict__ out_disp,
+                                                           float tau, uint8_t *__restrict__ out_rej)
 {
     __shared__ float wb[4];
     __shared__ int wa[4];
+    __shared__ float w2[UNIQ ? 4 : 1];
     const unsigned cnt = *counter;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 3, jj = lane & 7;
@@ -66,6 +74,8 @@ __global__ __launch_bounds__(256) void cv_wta_fixup_kernel(const float *__restri
         for (int m = 0; m < 8; m++) av[m] = own[p * 64 + 8 * m + jj];
         float best = __builtin_inff();
         int arg = -1;
+        UqChain ch;
+        ch.init();
         for (int db = dw; db < dwe; db += 8 * FX2_U) {
             float bv[FX2_U][8];
 #pragma unroll
@@ -85,11 +95,17 @@ __global__ __launch_bounds__(256) void cv_wta_fixup_kernel(const float *__restri
                 acc = acc + __shfl_xor(acc, 2, 64);   // ((acc0 + acc1) + (acc2 + acc3)), ...
                 acc = acc + __shfl_xor(acc, 4, 64);
                 const float c = (RIGHT ? x + d < W : x - d >= 0) ? -(0.0f + acc) : -0.0f;
-                if (d < dwe && c < best) {
+                if constexpr (UNIQ) {
+                    if (d < dwe) ch.take(c, d);
+                } else if (d < dwe && c < best) {
                     best = c;
                     arg = d;
                 }
             }
+        }
+        if constexpr (UNIQ) {
+            best = ch.b1;
+            arg = ch.a1;
         }
 #pragma unroll
         for (int off = 8; off < 64; off <<= 1) {
@@ -102,7 +118,26 @@ __global__ __launch_bounds__(256) void cv_wta_fixup_kernel(const float *__restri
             wa[wave] = arg;
         }
         __syncthreads();
-        if (threadIdx.x == 0) {
+        if constexpr (UNIQ) {
+            best = wb[0];
+            arg = wa[0];
+#pragma unroll
+            for (int v = 1; v < 4; v++) argmin_merge(best, arg, wb[v], wa[v]);
+            float c2 = ch.outside(arg);
+#pragma unroll
+            for (int off = 8; off < 64; off <<= 1) c2 = fminf(c2, __shfl_xor(c2, off, 64));
+            if (lane == 0) w2[wave] = c2;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                c2 = fminf(fminf(w2[0], w2[1]), fminf(w2[2], w2[3]));
+                const bool has = arg >= 0;
+                const bool rej = has && uq_margin(has, best, c2) < tau;
+                if (out_min) out_min[p] = best;
+                if (out_arg) out_arg[p] = arg;
+                if (out_disp) out_disp[p] = rej ? -1.0f : (float)arg;
+                if (out_rej) out_rej[p] = rej ? 1 : 0;
+            }
+        } else if (threadIdx.x == 0) {
             best = wb[0];
             arg = wa[0];
 #pragma unroll
@@ -177,7 +212,8 @@ SDE_EXPORT int sde_cv_wta_split(const float *fl, const float *fr, const uint16_t
         fl, fr, reinterpret_cast<const uint4 *>(fl_hi), reinterpret_cast<const uint4 *>(fl_lo), fl_norm,
         reinterpret_cast<const uint4 *>(fr_hi), reinterpret_cast<const uint4 *>(fr_lo), fr_norm, H, W, d0, d1,
         min_cost, argmin, disp, ws.counter, ws.list);
-    cv_wta_fixup_kernel<false><<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, ws.counter, ws.list, min_cost, argmin, disp);
+    cv_wta_fixup_kernel<false><<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, ws.counter, ws.list, min_cost, argmin, disp,
+                                                      0.0f, nullptr);
     return launch_status();
 }
 
@@ -206,8 +242,8 @@ static int cv_wta_view(bool right, const float *fl, const float *fr, int H, int 
     };
     // exact resolution of the pixels a sweep over [a, b) listed
     auto fixup = [&](int a, int b, unsigned *cnt, const int32_t *lst, float *mn, int32_t *ag, float *dp) {
-        if (right) cv_wta_fixup_kernel<true><<<1024, 256, 0, st>>>(fr, fl, W, a, b, cnt, lst, mn, ag, dp);
-        else cv_wta_fixup_kernel<false><<<1024, 256, 0, st>>>(fl, fr, W, a, b, cnt, lst, mn, ag, dp);
+        if (right) cv_wta_fixup_kernel<true><<<1024, 256, 0, st>>>(fr, fl, W, a, b, cnt, lst, mn, ag, dp, 0.0f, nullptr);
+        else cv_wta_fixup_kernel<false><<<1024, 256, 0, st>>>(fl, fr, W, a, b, cnt, lst, mn, ag, dp, 0.0f, nullptr);
     };
     if (C == 64 && mode == SDE_CV_CERTIFIED) {
         // The row-sweep kernel straight from the fp32 features (cv_row.hip) + the exact fix-ups of the pixels it
@@ -265,6 +301,42 @@ SDE_EXPORT int sde_cv_wta_right(const float *fl, const float *fr, int H, int W, 
 {
     return cv_wta_view(true, fl, fr, H, W, C, d0, d1, disp, min_cost, argmin, mode, workspace, workspace_bytes,
                        stream);
+}
+
+// sdu_cv_wta_unique: cv_wta_view's dispatch with the uniqueness check.  Certified mode covers one row sweep
+// (row_cert_supported); a wider range takes the exact form, which gives the same bytes, with the counters zeroed --
+// the precedent of ranges past CERT_COUNTERS chunks (carrying the runner-up across chunk merges is not built).
+SDE_EXPORT int sdu_cv_wta_unique(const float *fl, const float *fr, int H, int W, int C, int d0, int d1, int side,
+                                 float tau, float *disp, float *min_cost, int32_t *argmin, uint8_t *reject, int mode,
+                                 void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!fl || !fr || H <= 0 || W <= 0 || C <= 0 || d0 < 0 || d1 <= d0) return SDE_ERR_ARG;
+    if (!disp && !min_cost && !argmin && !reject) return SDE_ERR_ARG;
+    if (mode != SDE_CV_EXACT && mode != SDE_CV_CERTIFIED) return SDE_ERR_ARG;
+    if (side != SDE_SIDE_LEFT && side != SDE_SIDE_RIGHT) return SDE_ERR_ARG;
+    if (!uq_tau_ok(tau)) return SDE_ERR_ARG;
+    const bool right = side == SDE_SIDE_RIGHT;
+    hipStream_t st = as_stream(stream);
+    if (C == 64 && mode == SDE_CV_CERTIFIED) {
+        if (!workspace || workspace_bytes < sde_cv_wta_workspace_bytes(H, W)) return SDE_ERR_WORKSPACE;
+        const CertWs ws = cert_ws(workspace, H, W, 0);
+        if (hipMemsetAsync(ws.counter, 0, CERT_COUNTERS * sizeof(unsigned), st) != hipSuccess) return SDE_ERR_LAUNCH;
+        if (row_cert_supported(d0, d1)) {
+            launch_row_cert_unique(fl, fr, H, W, d0, d1, tau, min_cost, argmin, disp, reject, ws.counter, ws.list, st,
+                                   right);
+            if (right)
+                cv_wta_fixup_kernel<true, true><<<1024, 256, 0, st>>>(fr, fl, W, d0, d1, ws.counter, ws.list, min_cost,
+                                                                       argmin, disp, tau, reject);
+            else
+                cv_wta_fixup_kernel<false, true><<<1024, 256, 0, st>>>(fl, fr, W, d0, d1, ws.counter, ws.list, min_cost,
+                                                                        argmin, disp, tau, reject);
+        } else {
+            launch_cv_unique_exact(right, fl, fr, H, W, 64, d0, d1, tau, disp, min_cost, argmin, reject, st);
+        }
+    } else {
+        launch_cv_unique_exact(right, fl, fr, H, W, C, d0, d1, tau, disp, min_cost, argmin, reject, st);
+    }
+    return launch_status();
 }
 
 SDE_EXPORT int sde_argmin_merge(const float *mins, const int32_t *args, int nshards, int64_t npix, float *disp,

@@ -1,7 +1,7 @@
 """Drop-in for the reference's match.py batch entry point (match.py:19-103).
 
     python -m scenedepthestimation_amd.match [-g GPUS] [--checkpoint PATH|synthetic] [--cpu-path]
-           [--subpixel] [--bilateral] [--calib FILE [--depth-out DIR]] [--speckle-size N [--speckle-range X]]
+           [--subpixel] [--bilateral] [--calib FILE [--depth-out DIR]] [--unique X] [--speckle-size N [--speckle-range X]]
 
 Loops over ``./test/left_{i}.jpg`` / ``right_{i}.jpg`` for i = 1..18 (match.py:46),
 builds the tower once (weights packed and uploaded once, like the single TF
@@ -13,6 +13,7 @@ bilateral filter the reference carries commented out (process_functional.py:813-
 belongs to the SGM path (it filters the median's output).  --calib FILE (new): the inputs are raw camera images
 of one rig, rectified on the device from the calibration FILE (rectify.StereoCalibration) before anything else sees
 them; --depth-out DIR then also writes ``DIR/depth{i}.pfm`` (rectify.Rectifier.depth).  Without them nothing changes.
+--unique X (new; off by default): the uniqueness check with the absolute margin X (see match_single).
 --speckle-size N (new; 0 = off): speckle removal as the last stage (see match_single).
 
 Multi-GPU (new; the reference has none): under torchrun every rank takes pairs
@@ -26,7 +27,7 @@ import sys
 
 import numpy as np
 
-from .local_method import add_speckle_flags, speckle_option
+from .local_method import add_speckle_flags, add_unique_flag, speckle_option, unique_option
 from .match_single import DEFAULT_CKPT, normalise, rectified_pair, write_depth
 
 
@@ -47,6 +48,7 @@ def build_parser():
     p.add_argument("--calib", type=str, default=None,
                    help="stereo calibration (.npz / .json): the inputs are raw images, rectified on the device")
     p.add_argument("--depth-out", type=str, default=None, help="with --calib: a directory for depth{i}.pfm")
+    add_unique_flag(p)
     add_speckle_flags(p)
     return p
 
@@ -59,6 +61,7 @@ def main(argv=None):
     if args.depth_out and not args.calib:
         parser.error("--depth-out needs --calib (depth comes from the calibration's Q)")
     speckle = speckle_option(parser, args)
+    unique = unique_option(parser, args)
     if "WORLD_SIZE" not in os.environ:
         os.environ["HIP_VISIBLE_DEVICES"] = args.gpu     # match.py:24 (CUDA_VISIBLE_DEVICES)
     import torch
@@ -86,7 +89,7 @@ def main(argv=None):
         H, W = _l.shape
         if matcher is None or (matcher.H, matcher.W) != (H, W):
             matcher = StereoMatcher(H, W, args.ndisp, weights=weights, subpixel=args.subpixel,
-                                    bilateral=args.bilateral, speckle=speckle)
+                                    bilateral=args.bilateral, speckle=speckle, unique=unique)
         import time
         t0 = time.time()
         # the 5-pixel zero padding of process_functional.py:13-19 (match.py:58-63)
@@ -95,7 +98,10 @@ def main(argv=None):
         torch.cuda.synchronize()
         detail_time[0] += time.time() - t0
         if args.cpu_path:
-            disp = ops.cv_wta(fl, fr, 0, args.ndisp)[0]
+            if unique is not None:
+                disp = ops.cv_wta_unique(fl, fr, 0, args.ndisp, unique, want=("disp",))[0]
+            else:
+                disp = ops.cv_wta(fl, fr, 0, args.ndisp)[0]
             if args.subpixel:
                 ops.cv_subpixel(fl, fr, 0, args.ndisp, disp, "left", out=disp)
             if speckle is not None:

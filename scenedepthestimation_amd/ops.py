@@ -737,6 +737,69 @@ def cv_subpixel(fl, fr, d0: int, d1: int, disp, side: str = "left", out=None):
     return out
 
 
+# ----------------------------------------------------------------------------
+# Uniqueness check (build-defined; definition in include/sde_unique.h)
+# ----------------------------------------------------------------------------
+def unique_tau(tau) -> float:
+    """tau as the float32 the kernels compare against: a finite number >= 0."""
+    with np.errstate(over="ignore"):
+        t = float(np.float32(tau))
+    if not (0.0 <= t < float("inf")):
+        raise ValueError(f"the uniqueness margin must be a finite float32 >= 0 (got {tau!r})")
+    return t
+
+
+def wta_unique(vol, tau: float, layout: str = "DHW", rule: str = "inf", disp=None, want=("margin", "reject"),
+               margin=None, reject=None):
+    """The uniqueness check on a stored volume (sdu_wta_unique): with i = wta(vol, layout, rule)'s winner, c1 its
+    cost and c2 the smallest cost at |d - i| >= 2 (+inf if there is none), margin = 0 if c2 == c1 else c2 - c1 and
+    reject = margin < tau.  `disp`, when given, is masked in place: -1 where rejected, untouched elsewhere (so a
+    map wta_subpixel refined keeps its fractions).  Returns (margin f32, reject u8): each is written when named in
+    `want` or given, None otherwise."""
+    if vol.dim() != 3:
+        raise ValueError("volume must be 3-D")
+    if layout == "DHW":
+        D, H, W = vol.shape
+    else:
+        H, W, D = vol.shape
+    pv = _need(vol, "volume")
+    if "margin" in want and margin is None:
+        margin = _empty((H, W), torch.float32, vol)
+    if "reject" in want and reject is None:
+        reject = _empty((H, W), torch.uint8, vol)
+    pm = _need(margin, "margin", shape=(H, W)) if margin is not None else None
+    pr = _need(reject, "reject", dtype=torch.uint8, shape=(H, W)) if reject is not None else None
+    pd = _need(disp, "disp", shape=(H, W)) if disp is not None else None
+    check(lib.sdu_wta_unique(pv, H, W, D, LAYOUTS[layout], RULES[rule], ctypes.c_float(unique_tau(tau)), pm, pr, pd,
+                             _stream()), "sdu_wta_unique")
+    return margin, reject
+
+
+def cv_wta_unique(fl, fr, d0: int, d1: int, tau: float, side: str = "left", disp=None, min_cost=None, argmin=None,
+                  reject=None, want=("disp", "reject"), mode: str = "certified", workspace=None):
+    """cv_wta (side 'left') or cv_wta_right ('right') with the uniqueness check (sdu_cv_wta_unique): disp is -1
+    where the winner's margin over the best cost at |d - i| >= 2 is below tau, min_cost / argmin stay the winner's,
+    reject (u8) is the decision.  Modes, workspace and cv_wta_fixups as for cv_wta (identical outputs; the
+    certified row sweep decides a pixel only when its fast margin is further from tau than the error bound).
+    Returns (disp, min_cost, argmin, reject)."""
+    pl, pr, H, W, C = _feat_pair(fl, fr)
+    if side not in SIDES:
+        raise ValueError(f"side must be 'left' or 'right' (got {side!r})")
+    (disp, min_cost, argmin), (pd, pm, pa) = _wta_outputs(fl, H, W, want, disp, min_cost, argmin)
+    if "reject" in want and reject is None:
+        reject = _empty((H, W), torch.uint8, fl)
+    prj = _need(reject, "reject", dtype=torch.uint8, shape=(H, W)) if reject is not None else None
+    md = CV_MODES[mode]
+    pws, wsb = None, 0
+    if md == _lib.SDE_CV_CERTIFIED:
+        if workspace is None:
+            workspace = torch.empty(cv_wta_workspace_bytes(H, W), dtype=torch.uint8, device=fl.device)
+        pws, wsb = _need(workspace, "workspace", dtype=torch.uint8), workspace.numel()
+    check(lib.sdu_cv_wta_unique(pl, pr, H, W, C, int(d0), int(d1), SIDES[side], ctypes.c_float(unique_tau(tau)), pd, pm, pa,
+                                prj, md, pws, wsb, _stream()), "sdu_cv_wta_unique")
+    return disp, min_cost, argmin, reject
+
+
 def bilateral9(img_u8, src, out=None):
     """Bilateral_Filter_kernel (process_functional.py:882-974) for one view: the 9x9 window of `src` f32 [H,W]
     weighted by the intensity difference in img_u8 [H,W] (taps with a difference of 5 or more are rejected, zero

@@ -141,8 +141,11 @@ class StereoMatcher:
                  nf: int = 64, device=None, d_range=None, sgm: bool = False, tower_precision: str = "f16x3",
                  cv_mode: str = "certified", cbca_iters: int = 0, cbca_L1: int = 14, cbca_tau: float = 0.02,
                  emit_split: bool = False, sgm_placement_trials: int = SGM_PLACEMENT_TRIALS,
-                 subpixel: bool = False, bilateral: bool = False, speckle=None):
+                 subpixel: bool = False, bilateral: bool = False, speckle=None, unique=None):
         self.H, self.W, self.D = int(height), int(width), int(ndisp)
+        # unique=tau: the uniqueness check (include/sde_unique.h) inside the fused CV + WTA of match() / match_lr()
+        # and on the SGM path's S volumes; None (the default) leaves every path's launches and allocations as they are
+        self.unique = None if unique is None else ops.unique_tau(unique)
         # the two stages the reference carries switched off (process_functional.py:813-819, :882-974); off by
         # default, and with both off every call below makes the launches it made before they existed
         self.subpixel, self.bilateral = bool(subpixel), bool(bilateral)
@@ -164,6 +167,10 @@ class StereoMatcher:
             # a shard's map is not the final one: a region may exist only after the merge
             raise ValueError(f"speckle needs the whole disparity range [0, {self.D}); this matcher holds the shard "
                              f"[{self.d0}, {self.d1}): filter the merged map instead (ops.speckle)")
+        if self.unique is not None and (self.d0, self.d1) != (0, self.D):
+            # a shard's runner-up may sit in another shard: the merge of per-shard margins is not built
+            raise ValueError(f"unique needs the whole disparity range [0, {self.D}); this matcher holds the shard "
+                             f"[{self.d0}, {self.d1})")
         w = mc_cnn.load_weights(weights, self.nlayers)
         hw, hb = mc_cnn.layer_lists(w, self.nlayers)
         packed = ops.pack_tower_weights(hw, hb)
@@ -186,6 +193,7 @@ class StereoMatcher:
         self.min_cost = torch.empty((H, W), dtype=torch.float32, device=dev)
         self.argmin = torch.empty((H, W), dtype=torch.int32, device=dev)
         self.cv_mode = cv_mode
+        self.reject = torch.empty((H, W), dtype=torch.uint8, device=dev) if self.unique is not None else None
         self.cv_ws = torch.empty(ops.cv_wta_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
         # optional: bf16 split planes + norm bounds emitted by the tower's last layer, consumed by
         # sde_cv_wta_split.  The default certified path (sde_cv_wta, row-sweep kernel) splits the fp32
@@ -201,7 +209,7 @@ class StereoMatcher:
         # the z-normalised images
         self.sgm = SgmPath(H, W, self.D, dev, self.cbca_iters, self.cbca_L1, self.cbca_tau, self.subpixel,
                            self.bilateral, self.sgm_placement_trials, scratch=(self.img_pad, self.stats, L),
-                           speckle=self.speckle)
+                           speckle=self.speckle, unique=self.unique)
         if sgm:
             self.sgm.alloc()
 
@@ -224,6 +232,12 @@ class StereoMatcher:
     def speckle_sizes(self):
         """i32 [H,W], the region size of every valid pixel of the last map filtered (None as speckle_mask)."""
         return None if self.speckle is None else self.speckle.sizes
+
+    @property
+    def unique_mask(self):
+        """u8 [H,W], 1 where the last match() / match_lr() / cost_wta() rejected a left-view winner by the
+        uniqueness check (None with the option off); the SGM path keeps its own (sgm.unique_mask)."""
+        return self.reject
 
     @property
     def ws(self):
@@ -292,7 +306,15 @@ class StereoMatcher:
     def cost_wta(self, want=("disp",)):
         """Fused cost volume + WTA over this matcher's disparity range [d0, d1).  In certified mode with
         emit_split=True the tower-emitted split planes are used (sde_cv_wta_split) when the current
-        features came from this matcher's tower; otherwise sde_cv_wta reads the fp32 features."""
+        features came from this matcher's tower; otherwise sde_cv_wta reads the fp32 features.  With unique set
+        the fused unique form (ops.cv_wta_unique) on the fp32 features: disp is -1 where rejected, unique_mask the
+        decision."""
+        if self.unique is not None:
+            return ops.cv_wta_unique(self.feat[0], self.feat[1], self.d0, self.d1, self.unique, "left",
+                                     disp=self.disp if "disp" in want else None,
+                                     min_cost=self.min_cost if "min" in want else None,
+                                     argmin=self.argmin if "argmin" in want else None, reject=self.reject, want=(),
+                                     mode=self.cv_mode, workspace=self.cv_ws)[:3]
         if self.cv_mode == "certified" and self.split_valid:
             return ops.cv_wta_split(self.feat[0], self.feat[1], self.split[0], self.split[1], self.d0, self.d1,
                                     disp=self.disp if "disp" in want else None,
@@ -307,7 +329,8 @@ class StereoMatcher:
 
     def match(self):
         """One pass of the hot path on the resident images: features + fused CV/WTA -> disparity; with
-        subpixel=True followed by the parabola step on the winner's recomputed neighbours (ops.cv_subpixel).  With
+        subpixel=True followed by the parabola step on the winner's recomputed neighbours (ops.cv_subpixel), which
+        passes the -1 of a pixel the uniqueness check rejected (unique=tau) through.  With
         speckle set the filtered map is returned, in a buffer of its own; self.disp keeps the unfiltered one."""
         self.features()
         self.cost_wta()
@@ -327,6 +350,7 @@ class StereoMatcher:
             self.min_cost_r = torch.empty((H, W), dtype=torch.float32, device=dev)
             self.argmin_r = torch.empty((H, W), dtype=torch.int32, device=dev)
             self.cv_ws_r = torch.empty(ops.cv_wta_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
+            self.reject_r = torch.empty((H, W), dtype=torch.uint8, device=dev) if self.unique is not None else None
             self.checked = CheckedPath(H, W, dev, self.bilateral, self.speckle)
             self.lr_bufs = self.checked.bufs
         return self.lr_bufs
@@ -336,6 +360,12 @@ class StereoMatcher:
         argmin_r with its own workspace cv_ws_r.  Always reads the fp32 features (there is no right-view form
         of the pre-split kernel)."""
         self._lr_bufs()
+        if self.unique is not None:
+            return ops.cv_wta_unique(self.feat[0], self.feat[1], self.d0, self.d1, self.unique, "right",
+                                     disp=self.disp_r if "disp" in want else None,
+                                     min_cost=self.min_cost_r if "min" in want else None,
+                                     argmin=self.argmin_r if "argmin" in want else None, reject=self.reject_r, want=(),
+                                     mode=self.cv_mode, workspace=self.cv_ws_r)[:3]
         return ops.cv_wta_right(self.feat[0], self.feat[1], self.d0, self.d1,
                                 disp=self.disp_r if "disp" in want else None,
                                 min_cost=self.min_cost_r if "min" in want else None,
@@ -351,7 +381,9 @@ class StereoMatcher:
         """match_lr's stages after the features, on the features this matcher currently holds.  subpixel=True
         refines both views' raw maps before the check; bilateral=True filters the median's output with the left
         image (the reference's dead call, :1260, would filter the LRC-filled map and overwrite the median's
-        result: a documented divergence); speckle removal, when set, comes last."""
+        result: a documented divergence); speckle removal, when set, comes last.  With
+        unique=tau both views come from the fused unique form: a rejected pixel is -1 in its raw map, which the
+        check flags (d < 0), so rejected left pixels are filled by the LRC fill."""
         self._need_whole_range()
         self._lr_bufs()
         self.cost_wta()
@@ -423,13 +455,15 @@ class SgmPath:
     cbca_iters > 0 puts cross-based aggregation (build-defined; 0 = the reference's path) before SGM; its arms come
     from the z-normalised images, which need scratch = (img_pad, stats, pad): two f32 [H+2p, W+2p] buffers and
     two ops.preprocess_scratch_bytes(H, W) scratch tensors (StereoMatcher lends the tower's input buffers).
-    subpixel / bilateral: the two stages the reference carries switched off (see run).  speckle: None, a
+    subpixel / bilateral: the two stages the reference carries switched off (see run).  unique=tau: the uniqueness
+    check on the final S volumes (see run; unique_mask is the left view's decision).  speckle: None, a
     (max_size, max_diff) pair or a SpeckleStage to share; with post=True the maps run() returns are filtered."""
 
     def __init__(self, height: int, width: int, ndisp: int, device, cbca_iters: int = 0, cbca_L1: int = 14,
                  cbca_tau: float = 0.02, subpixel: bool = False, bilateral: bool = False,
-                 placement_trials: int = SGM_PLACEMENT_TRIALS, scratch=None, speckle=None):
+                 placement_trials: int = SGM_PLACEMENT_TRIALS, scratch=None, speckle=None, unique=None):
         self.H, self.W, self.D, self.device = int(height), int(width), int(ndisp), torch.device(device)
+        self.unique = None if unique is None else ops.unique_tau(unique)
         self.cbca_iters, self.cbca_L1, self.cbca_tau = int(cbca_iters), int(cbca_L1), float(cbca_tau)
         self.subpixel, self.bilateral = bool(subpixel), bool(bilateral)
         self.placement_trials = int(placement_trials)
@@ -512,10 +546,17 @@ class SgmPath:
                 disp_a=torch.empty((H, W), dtype=torch.float32, device=dev),
                 disp_b=torch.empty((H, W), dtype=torch.float32, device=dev),
             )
+        if self.unique is not None and "rej" not in self.bufs:
+            self.bufs["rej"] = [torch.empty((H, W), dtype=torch.uint8, device=dev) for _ in range(2)]
         if (arms or self.cbca_iters > 0) and "arms" not in self.bufs:
             self.bufs["arms"] = [torch.empty((H, W), dtype=torch.int32, device=dev) for _ in range(2)]
             self.bufs["cbca_ws"] = torch.empty((ops.cbca_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
         return self.bufs
+
+    @property
+    def unique_mask(self):
+        """u8 [H,W], 1 where the last run() rejected a left-view winner (None with the option off or before it)."""
+        return None if self.unique is None or self.bufs is None else self.bufs["rej"][0]
 
     def cbca(self, cv_l, cv_r, img_l, img_r):
         """Cross-based aggregation (build-defined) of the left [H,W,D] volume in
@@ -545,6 +586,10 @@ class SgmPath:
         """process_functional.py:1093-1267 on device tensors; returns (disp_l, disp_r).  subpixel=True: the
         unfused SGM pair followed by ops.wta_subpixel per side instead of the fused last direction;
         bilateral=True: the 9x9 bilateral filter of each median-filtered map with its own image.
+        unique=tau: the unfused pair as for subpixel, ops.wta or ops.wta_subpixel per side, then ops.wta_unique per
+        side on S (rule d0).  With post=False both maps carry -1 at their rejected pixels.  With post=True the
+        left-right check runs on the unmasked maps, the left reject mask is OR-ed into lrc_l before the LRC fill
+        (rejected left pixels are filled), and the right map gets its -1 after its median or bilateral filter.
 
         timings: optional dict receiving per-stage seconds (synchronised)."""
         import time
@@ -572,13 +617,23 @@ class SgmPath:
         # both sides per launch (the reference's k loop); S := 8-path sum, no zero-fill pass
         # penalties from sgm_penalties (channels 0/1 zero), finite costs: DU folds into UD;
         # WTA_and_SupixelRefinement_kernel (:800-837) fused into the last direction
-        if self.subpixel:
-            # the parabola step needs the final S around the winner, which the fused last direction never
-            # stores: the unfused pair (S written in full), then WTA + refinement per side
+        if self.subpixel or self.unique is not None:
+            # the parabola step needs the final S around the winner, and the uniqueness check the whole of it,
+            # which the fused last direction never stores: the unfused pair (S written in full), then WTA
+            # (+ refinement) per side
             ops.sgm_8path_pair(b["cv"][0], b["pen"][0], b["S"][0], b["cv"][1], b["pen"][1], b["S"][1],
                                zero_du_penalties=True)
-            ops.wta_subpixel(b["S"][0], "HWD", "d0", out=b["disp"][0])
-            ops.wta_subpixel(b["S"][1], "HWD", "d0", out=b["disp"][1])
+            wta = ops.wta_subpixel if self.subpixel else ops.wta
+            wta(b["S"][0], "HWD", "d0", out=b["disp"][0])
+            wta(b["S"][1], "HWD", "d0", out=b["disp"][1])
+            if self.unique is not None:
+                # post=False: both maps masked here.  post=True: the left decision only (for lrc_l); the right
+                # map is masked after its filters, by the launch that takes its decision
+                ops.wta_unique(b["S"][0], self.unique, "HWD", "d0", disp=None if post else b["disp"][0], want=(),
+                               reject=b["rej"][0])
+                if not post:
+                    ops.wta_unique(b["S"][1], self.unique, "HWD", "d0", disp=b["disp"][1], want=(),
+                                   reject=b["rej"][1])
         else:
             ops.sgm_8path_wta_pair(b["cv"][0], b["pen"][0], b["S"][0], b["disp"][0], b["cv"][1], b["pen"][1],
                                    b["S"][1], b["disp"][1], zero_du_penalties=True)
@@ -588,6 +643,8 @@ class SgmPath:
         b["lrc"][0].zero_()
         b["lrc"][1].zero_()
         ops.lr_check(b["disp"][0], b["disp"][1], b["lrc"][0], b["lrc"][1])
+        if self.unique is not None:
+            b["lrc"][0].bitwise_or_(b["rej"][0])
         ops.lrc_fill(b["disp"][0], b["lrc"][0], out=b["disp_a"])
         t = mark("lrc", t)
         # Median_Filter_kernel(d_disparityl_a, d_disparityr_a, d_disparityl, d_disparityr) (:1250):
@@ -607,6 +664,8 @@ class SgmPath:
             final = (b["disp_a"], b["disp_b"])
         else:
             final = (b["disp"][0], b["disp"][1])
+        if self.unique is not None:
+            ops.wta_unique(b["S"][1], self.unique, "HWD", "d0", disp=final[1], want=(), reject=b["rej"][1])
         if self.speckle is not None:
             # the right map first: the stage's mask and sizes are then the left map's
             right = self.speckle.run(final[1], slot=1)

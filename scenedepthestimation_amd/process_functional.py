@@ -100,7 +100,7 @@ def add_detail_time(detail_time, timings):
 
 
 def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, ndisp=128, subpixel=False,
-                             bilateral=False):
+                             bilateral=False, unique=None):
     """GPU path (process_functional.py:1093-1267): cost volume [H,W,D] (L, R; 1.0 fill),
     SGM penalties, 8-path SGM, WTA, LR check + LRC fill, 5x5 median.
 
@@ -108,7 +108,8 @@ def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, 
     reference: [1] cost volume, [3] SGM, [4] WTA, [5] LR check, [6] filtering (seconds).
     ``ndisp`` defaults to the reference's hard-coded 128 (:1111).  ``subpixel`` / ``bilateral`` switch on the two
     stages the reference carries commented out: the parabola step of the WTA kernel (:813-819) and
-    Bilateral_Filter_kernel (:882-974), the latter applied to the median's output.
+    Bilateral_Filter_kernel (:882-974), the latter applied to the median's output.  ``unique`` (build-defined, off by
+    default): SgmPath's uniqueness check with that absolute margin.
     """
     assert imagel.shape == imager.shape                   # :1097
     H, W = imagel.shape[0:2]
@@ -118,7 +119,8 @@ def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, 
     if fl.shape[:2] != (H, W):
         raise ValueError("features and images differ in size")
     # cbca_iters = 0: the reference has no aggregation stage
-    path = SgmPath(H, W, int(ndisp), fl.device, cbca_iters=0, subpixel=subpixel, bilateral=bilateral)
+    path = SgmPath(H, W, int(ndisp), fl.device, cbca_iters=0, subpixel=subpixel, bilateral=bilateral,
+                   unique=unique)
     timings = {}
     dl, dr = path.run(fl, fr, il, ir, timings=timings)
     return dl.cpu().numpy(), dr.cpu().numpy(), add_detail_time(detail_time, timings)
