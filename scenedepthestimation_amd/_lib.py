@@ -1,5 +1,6 @@
 """ctypes binding of libsde.so (the C ABI declared in include/sde.h, the geometry stage's in include/sde_geom.h,
-the filters' in include/sde_filter.h and the uniqueness check's in include/sde_unique.h).
+the filters' in include/sde_filter.h, the uniqueness check's in include/sde_unique.h and the interpolation's in
+include/sde_interp.h).
 
 torch is imported first on purpose: its bundled HIP runtime (SONAME
 libamdhip64.so.7) is then the one libsde.so binds to, so device pointers and
@@ -18,12 +19,15 @@ import torch  # noqa: F401  (load torch's HIP runtime before libsde.so)
 
 from ._build import INCLUDE, LIB
 
-# function prefix -> the header that declares it; constants carry the prefix in capitals (SDE_*, SDG_*, SDF_*, SDU_*)
-HEADER_NAMES = {"sde": "sde.h", "sdg": "sde_geom.h", "sdf": "sde_filter.h", "sdu": "sde_unique.h"}
+# function prefix -> the header that declares it; constants carry the prefix in capitals (SDE_*, SDG_*, SDF_*, SDU_*,
+# SDI_*)
+HEADER_NAMES = {"sde": "sde.h", "sdg": "sde_geom.h", "sdf": "sde_filter.h", "sdu": "sde_unique.h",
+                "sdi": "sde_interp.h"}
 HEADER = os.path.join(INCLUDE, HEADER_NAMES["sde"])
 GEOM_HEADER = os.path.join(INCLUDE, HEADER_NAMES["sdg"])
 FILTER_HEADER = os.path.join(INCLUDE, HEADER_NAMES["sdf"])
 UNIQUE_HEADER = os.path.join(INCLUDE, HEADER_NAMES["sdu"])
+INTERP_HEADER = os.path.join(INCLUDE, HEADER_NAMES["sdi"])
 
 # every scalar type the headers may use; any pointer is a c_void_p.  A type outside this map is an error
 # (parse_header raises), never a guess: a wrong width is a silent miscall.
@@ -92,10 +96,13 @@ with open(FILTER_HEADER) as _fh:
     FILTER_SIGNATURES, FILTER_CONSTANTS = parse_header(_fh.read(), prefix="sdf")   # sdf_* / SDF_*
 with open(UNIQUE_HEADER) as _fh:
     UNIQUE_SIGNATURES, UNIQUE_CONSTANTS = parse_header(_fh.read(), prefix="sdu")   # sdu_* / SDU_*
+with open(INTERP_HEADER) as _fh:
+    INTERP_SIGNATURES, INTERP_CONSTANTS = parse_header(_fh.read(), prefix="sdi")   # sdi_* / SDI_*
 globals().update(CONSTANTS)   # _lib.SDE_LAYOUT_DHW, ... as module attributes
 globals().update(GEOM_CONSTANTS)
 globals().update(FILTER_CONSTANTS)
 globals().update(UNIQUE_CONSTANTS)
+globals().update(INTERP_CONSTANTS)
 
 
 class SdeError(RuntimeError):
@@ -108,7 +115,8 @@ def _load():
                           "(there is no CPU fallback)")
     lib = ctypes.CDLL(LIB)
     missing = []
-    for name, (res, args) in {**SIGNATURES, **GEOM_SIGNATURES, **FILTER_SIGNATURES, **UNIQUE_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **GEOM_SIGNATURES, **FILTER_SIGNATURES, **UNIQUE_SIGNATURES,
+                              **INTERP_SIGNATURES}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1,7 +1,8 @@
 """The reference's classical local matcher (local_mathod.py) on the GPU: SAD+SSD, rank and census.
 
     python -m scenedepthestimation_amd.local_method [-k 5] [--method ad|rank|census] [--ndisp 200]
-           [--lr-check] [--unique X] [--speckle-size N [--speckle-range X]] [--image-dir ./eval] [--out-dir ./result/SAD] [-n 5]
+           [--lr-check [--fill mean4|interpolate]] [--unique X] [--speckle-size N [--speckle-range X]]
+           [--image-dir ./eval] [--out-dir ./result/SAD] [-n 5]
 
 It needs no weights: two grayscale images in, a disparity map out.  For pair i in 0..n-1 it reads
 ``left_{i}.png`` / ``right_{i}.png`` from --image-dir and writes ``ld{i}.png`` as ``uint8(disparity)`` into
@@ -24,6 +25,9 @@ below the best cost at least two disparities away becomes -1.
 
 --speckle-size N (new; 0 = off) removes, as the last stage, every region of at most N pixels of the map as matched
 whose 4-neighbours differ by at most --speckle-range (include/sde_filter.h): its pixels become -1.
+
+--fill interpolate (new; the default mean4 is the reference's LRC fill), with --lr-check: the flagged left pixels are
+classified as occlusions or mismatches and interpolated (include/sde_interp.h).
 """
 from __future__ import annotations
 
@@ -36,7 +40,7 @@ METHODS = ("ad", "rank", "census")
 
 class LocalMatcher:
     def __init__(self, height: int, width: int, ndisp: int = 200, method: str = "ad", radius: int = 5, device=None,
-                 speckle=None, unique=None):
+                 speckle=None, unique=None, fill: str = "mean4"):
         import torch
 
         from . import ops
@@ -50,6 +54,8 @@ class LocalMatcher:
                 raise ValueError(f"radius must be in 0..{ops.LOCAL_MAX_RADIUS}")
             if self.W < self.D + 2 * self.k:
                 raise ValueError(window_rule(self.W, self.D, self.k))
+        # fill="interpolate": match_lr() classifies and interpolates its flagged pixels instead of LRC-filling them
+        self.fill = ops.fill_mode(fill)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         dev, H, W = self.device, self.H, self.W
         # both images in one allocation: the transforms run the pair per launch
@@ -123,7 +129,8 @@ class LocalMatcher:
 
             from .pipeline import CheckedPath
             self.disp_r = torch.empty((self.H, self.W), dtype=torch.float32, device=self.device)
-            self.checked = CheckedPath(self.H, self.W, self.device, speckle=self.speckle)
+            self.checked = CheckedPath(self.H, self.W, self.device, speckle=self.speckle, fill=self.fill,
+                                       ndisp=self.D)
             if self.unique is not None:
                 self.vol_r = torch.empty_like(self.vol)
                 self.reject_r = torch.empty_like(self.reject)
@@ -133,8 +140,9 @@ class LocalMatcher:
     def match_lr(self, max_diff: float = 1.0):
         """Census only: both views from one pass of the fused kernel, the wrap-free left-right check, the LRC
         fill of the left map and the 5x5 median into the interior of a copy of the filled map (the 2-pixel
-        border keeps the filled values), then speckle removal when set.  Returns (disp_l_checked, disp_r, lrc_l); self.disp keeps the raw left
-        map."""
+        border keeps the filled values), then speckle removal when set.  With fill="interpolate" the flagged left
+        pixels are classified and interpolated instead of LRC-filled.  Returns (disp_l_checked, disp_r, lrc_l);
+        self.disp keeps the raw left map."""
         from . import ops
         if self.method != "census":
             raise ValueError("match_lr needs method='census': the reference defines no right view for the "
@@ -167,12 +175,20 @@ def build_parser():
     p.add_argument("--ndisp", type=int, default=200, help="disparity range (the reference hard-codes 200)")
     p.add_argument("--lr-check", action="store_true",
                    help="with --method census: left-right check, LRC fill and 5x5 median on the two views")
+    add_fill_flag(p)
     add_unique_flag(p)
     add_speckle_flags(p)
     p.add_argument("--image-dir", type=str, default="./eval", help="directory of left_{i}.png / right_{i}.png")
     p.add_argument("--out-dir", type=str, default="./result/SAD", help="directory the ld{i}.png maps are written to")
     p.add_argument("-n", "--num", type=int, default=5, help="number of pairs (the reference loops over 5)")
     return p
+
+
+def add_fill_flag(p):
+    """--fill, shared by the command lines: what a left-right-checked path does with its flagged pixels."""
+    p.add_argument("--fill", choices=("mean4", "interpolate"), default="mean4",
+                   help="flagged pixels of a left-right-checked path: the reference's mean of four neighbours, or "
+                        "occlusion / mismatch interpolation")
 
 
 def add_unique_flag(p):
@@ -235,7 +251,8 @@ def run(args):
             parser.error(f"{lp}: " + window_rule(W, args.ndisp, args.kernel))
         if matcher is None or (matcher.H, matcher.W) != (H, W):
             matcher = LocalMatcher(H, W, args.ndisp, args.method, args.kernel,
-                                   speckle=getattr(args, "speckle", None), unique=getattr(args, "unique", None))
+                                   speckle=getattr(args, "speckle", None), unique=getattr(args, "unique", None),
+                                   fill=getattr(args, "fill", "mean4"))
         matcher.load_images(left, right)
         disp = matcher.match_lr()[0] if args.lr_check else matcher.match()
         path = os.path.join(args.out_dir, "ld{}.png".format(i))

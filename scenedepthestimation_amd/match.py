@@ -2,6 +2,7 @@
 
     python -m scenedepthestimation_amd.match [-g GPUS] [--checkpoint PATH|synthetic] [--cpu-path]
            [--subpixel] [--bilateral] [--calib FILE [--depth-out DIR]] [--unique X] [--speckle-size N [--speckle-range X]]
+           [--fill mean4|interpolate]
 
 Loops over ``./test/left_{i}.jpg`` / ``right_{i}.jpg`` for i = 1..18 (match.py:46),
 builds the tower once (weights packed and uploaded once, like the single TF
@@ -15,6 +16,7 @@ of one rig, rectified on the device from the calibration FILE (rectify.StereoCal
 them; --depth-out DIR then also writes ``DIR/depth{i}.pfm`` (rectify.Rectifier.depth).  Without them nothing changes.
 --unique X (new; off by default): the uniqueness check with the absolute margin X (see match_single).
 --speckle-size N (new; 0 = off): speckle removal as the last stage (see match_single).
+--fill interpolate (new; SGM path): occlusion / mismatch interpolation of the flagged pixels (see match_single).
 
 Multi-GPU (new; the reference has none): under torchrun every rank takes pairs
 i = rank+1, rank+1+N, ... (pair data-parallel, no collective).
@@ -27,7 +29,7 @@ import sys
 
 import numpy as np
 
-from .local_method import add_speckle_flags, add_unique_flag, speckle_option, unique_option
+from .local_method import add_fill_flag, add_speckle_flags, add_unique_flag, speckle_option, unique_option
 from .match_single import DEFAULT_CKPT, normalise, rectified_pair, write_depth
 
 
@@ -50,6 +52,7 @@ def build_parser():
     p.add_argument("--depth-out", type=str, default=None, help="with --calib: a directory for depth{i}.pfm")
     add_unique_flag(p)
     add_speckle_flags(p)
+    add_fill_flag(p)
     return p
 
 
@@ -60,6 +63,8 @@ def main(argv=None):
         parser.error("--bilateral filters the median's output: it belongs to the SGM path")
     if args.depth_out and not args.calib:
         parser.error("--depth-out needs --calib (depth comes from the calibration's Q)")
+    if args.fill != "mean4" and args.cpu_path:
+        parser.error("--fill fills what a left-right check flags: it belongs to the SGM path")
     speckle = speckle_option(parser, args)
     unique = unique_option(parser, args)
     if "WORLD_SIZE" not in os.environ:
@@ -89,7 +94,7 @@ def main(argv=None):
         H, W = _l.shape
         if matcher is None or (matcher.H, matcher.W) != (H, W):
             matcher = StereoMatcher(H, W, args.ndisp, weights=weights, subpixel=args.subpixel,
-                                    bilateral=args.bilateral, speckle=speckle, unique=unique)
+                                    bilateral=args.bilateral, speckle=speckle, unique=unique, fill=args.fill)
         import time
         t0 = time.time()
         # the 5-pixel zero padding of process_functional.py:13-19 (match.py:58-63)

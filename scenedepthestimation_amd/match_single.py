@@ -3,7 +3,7 @@
     python -m scenedepthestimation_amd.match_single [-g GPU] [-i ID] [-f FILE]
            [--checkpoint PATH|synthetic] [--cpu-path [--lr-check]] [--ndisp N] [--ui]
            [--subpixel] [--bilateral] [--calib FILE [--depth-out PATH]]
-           [--unique X] [--speckle-size N [--speckle-range X]]
+           [--unique X] [--speckle-size N [--speckle-range X]] [--fill mean4|interpolate]
 
 Same flags, paths and outputs as match_single.py:15-57 (and, with --ui,
 match_single_ui.py:20-58): reads ``./eval/left_{id}.png`` / ``right_{id}.png``
@@ -36,6 +36,10 @@ winner whose cost is less than X below the best cost at least two disparities aw
 --speckle-size N (new; 0 = off) removes, as the last stage of whichever path runs, every region of at most N pixels
 of the map as matched whose 4-neighbours differ by at most --speckle-range (default 1.0; include/sde_filter.h): its
 pixels become -1, which the PNG's uint8 cast shows as 255 and --depth-out as depth 0.
+
+--fill interpolate (new; the default mean4 is the reference's LRC fill) on the paths with a left-right check (the SGM
+path, --cpu-path --lr-check): a flagged left pixel is classified as an occlusion or a mismatch and takes the nearest
+good value on the background side or the median of the nearest good values along 16 rays (include/sde_interp.h).
 """
 from __future__ import annotations
 
@@ -45,7 +49,7 @@ import sys
 
 import numpy as np
 
-from .local_method import add_speckle_flags, add_unique_flag, speckle_option, unique_option
+from .local_method import add_fill_flag, add_speckle_flags, add_unique_flag, speckle_option, unique_option
 
 DEFAULT_CKPT = r"./check_points_11_11/model_epoch14.ckpt"   # match_single.py:46
 
@@ -73,6 +77,7 @@ def build_parser(ui: bool = False):
     p.add_argument("--depth-out", type=str, default=None, help="with --calib: write the depth map as a .pfm")
     add_unique_flag(p)
     add_speckle_flags(p)
+    add_fill_flag(p)
     return p
 
 
@@ -117,16 +122,18 @@ def parse_args(argv=None, ui: bool = False):
         p.error("--bilateral filters the median's output: use the SGM path or --cpu-path --lr-check")
     if args.depth_out and not args.calib:
         p.error("--depth-out needs --calib (depth comes from the calibration's Q)")
+    if args.fill != "mean4" and args.cpu_path and not args.lr_check:
+        p.error("--fill fills what a left-right check flags: use the SGM path or --cpu-path --lr-check")
     args.speckle = speckle_option(p, args)
     args.unique = unique_option(p, args)
     return args
 
 
 def lr_checked_disparity(left, right, ndisp, checkpoint, subpixel=False, bilateral=False, left_u8=None,
-                         speckle=None, unique=None):
+                         speckle=None, unique=None, fill="mean4"):
     """The --lr-check map: compute_feature's tower on the normalised images (the same padded input, so the same
     features as the plain --cpu-path run), then StereoMatcher.lr_checked on them.  bilateral=True needs the left
-    u8 image (the filter's intensities); speckle, unique: StereoMatcher's options."""
+    u8 image (the filter's intensities); speckle, unique, fill: StereoMatcher's options."""
     import torch
 
     from . import mc_cnn
@@ -134,7 +141,7 @@ def lr_checked_disparity(left, right, ndisp, checkpoint, subpixel=False, bilater
     nlayers = 11 // 2
     H, W = left.shape[:2]
     m = StereoMatcher(H, W, ndisp, weights=mc_cnn.load_weights(checkpoint, nlayers), nlayers=nlayers,
-                      subpixel=subpixel, bilateral=bilateral, speckle=speckle, unique=unique)
+                      subpixel=subpixel, bilateral=bilateral, speckle=speckle, unique=unique, fill=fill)
     if bilateral:
         m.img_u8[0].copy_(torch.from_numpy(np.ascontiguousarray(left_u8, np.uint8)))
     m.load_normalised(left[..., 0], right[..., 0])
@@ -167,9 +174,10 @@ def run(args) -> str:
     right = normalise(_right.astype(np.float32))
     subpixel, bilateral = getattr(args, "subpixel", False), getattr(args, "bilateral", False)
     speckle, unique = getattr(args, "speckle", None), getattr(args, "unique", None)
+    fill = getattr(args, "fill", "mean4")
     if args.cpu_path and getattr(args, "lr_check", False):
         disp = lr_checked_disparity(left, right, args.ndisp, args.checkpoint, subpixel, bilateral, _left, speckle,
-                                    unique)
+                                    unique, fill)
     else:
         fl, fr = compute_feature(left, right, 11, 11, 64, args.checkpoint)
         if args.cpu_path and (subpixel or unique is not None):
@@ -187,7 +195,8 @@ def run(args) -> str:
         else:
             detail_time = np.zeros(shape=[7], dtype=np.float32)
             disp, _, detail_time = disparity_compute_by_gpu(_left, _right, fl, fr, detail_time, ndisp=args.ndisp,
-                                                            subpixel=subpixel, bilateral=bilateral, unique=unique)
+                                                            subpixel=subpixel, bilateral=bilateral, unique=unique,
+                                                            fill=fill)
         if speckle is not None:
             disp = speckle_filtered(disp, speckle)
     out = disp.astype("uint8") * 2 if args.ui else disp.astype("uint8")

@@ -1161,3 +1161,67 @@ def speckle(disp, max_size: int, max_diff: float = 1.0, fill: float = -1.0, out=
                           _need(out, "out", shape=(H, W)), pm, ps, workspace.data_ptr(),
                           workspace.numel() * workspace.element_size(), _stream()), "sdf_speckle")
     return out, mask, sizes
+
+
+# ---------------------------------------------------------------- interpolation (include/sde_interp.h)
+SIDES = {"left": SDE_SIDE_LEFT, "right": SDE_SIDE_RIGHT}
+# what a checked path does with its flagged pixels: sde_lrc_fill, or classify + interpolate
+FILLS = ("mean4", "interpolate")
+
+
+def fill_mode(fill) -> str:
+    """A checked path's fill= option, or ValueError."""
+    if fill not in FILLS:
+        raise ValueError(f"fill must be one of {FILLS}, got {fill!r}")
+    return fill
+
+
+def _side(side):
+    if side not in SIDES:
+        raise ValueError("side must be 'left' or 'right'")
+    return SIDES[side]
+
+
+def classify(disp_other, lrc, ndisp: int, side: str = "left", max_diff: float = 1.0, out=None):
+    """Flagged pixels of one view into occlusions and mismatches (sdi_classify) -> cls u8 [H,W]: 0 unflagged
+    (lrc byte != 1), 2 where some integer disparity in [0, ndisp) makes the pixel consistent with the OTHER view's
+    map disp_other within max_diff, 1 otherwise.  out=lrc classifies in place."""
+    if disp_other.dim() != 2:
+        raise ValueError(f"disp_other must be [H,W], got {tuple(disp_other.shape)}")
+    H, W = disp_other.shape
+    if out is None:
+        out = _empty((H, W), torch.uint8, disp_other)
+    check(lib.sdi_classify(_need(disp_other, "disp_other"), _need(lrc, "lrc", dtype=torch.uint8, shape=(H, W)), H, W,
+                           int(ndisp), _side(side), float(max_diff), _need(out, "out", dtype=torch.uint8, shape=(H, W)),
+                           _stream()), "sdi_classify")
+    return out
+
+
+def interpolate_workspace_bytes(H: int, W: int) -> int:
+    """Bytes of sdi_interpolate's workspace for an H x W map (sdi_interpolate_workspace_bytes)."""
+    return int(lib.sdi_interpolate_workspace_bytes(int(H), int(W)))
+
+
+def interpolate(disp, cls, side: str = "left", out=None, filled=None, want=("out",), workspace=None):
+    """Interpolation of the classified pixels of an f32 [H,W] map (sdi_interpolate) -> (out f32, filled u8): an
+    occlusion (cls 1) takes the nearest source of its row on the background side (left of it for the left view),
+    a mismatch (cls 2) the median of the first sources along 16 rays; a source is a cls-0 pixel with a finite
+    value >= 0.  out must not be disp.  filled (1 where a value was taken) when given or named in `want`, else
+    None.  workspace: a GPU tensor of interpolate_workspace_bytes(H, W) bytes, 4-byte aligned, contents arbitrary;
+    one is allocated when absent."""
+    if disp.dim() != 2:
+        raise ValueError(f"disp must be [H,W], got {tuple(disp.shape)}")
+    H, W = disp.shape
+    if out is None:
+        out = _empty((H, W), torch.float32, disp)
+    if filled is None and "filled" in want:
+        filled = _empty((H, W), torch.uint8, disp)
+    if workspace is None:
+        workspace = _empty((interpolate_workspace_bytes(H, W),), torch.uint8, disp)
+    elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
+        raise ValueError("interpolate workspace must be a contiguous GPU tensor")
+    pf = None if filled is None else _need(filled, "filled", dtype=torch.uint8, shape=(H, W))
+    check(lib.sdi_interpolate(_need(disp, "disp"), _need(cls, "cls", dtype=torch.uint8, shape=(H, W)), H, W,
+                              _side(side), _need(out, "out", shape=(H, W)), pf, workspace.data_ptr(),
+                              workspace.numel() * workspace.element_size(), _stream()), "sdi_interpolate")
+    return out, filled

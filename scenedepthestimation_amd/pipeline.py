@@ -128,6 +128,35 @@ class SpeckleStage:
         return self.out[slot]
 
 
+class InterpStage:
+    """fill="interpolate" of a checked path (include/sde_interp.h): the flagged pixels of the left map are
+    classified against the right map (ops.classify, the path's flags, the matcher's D) and interpolated
+    (ops.interpolate) where fill="mean4" runs ops.lrc_fill.  The class map, the filled mask and the workspace are
+    allocated on first use.  No later stage reads `cls` or `filled`: they are kept for the caller, as
+    SpeckleStage.mask is (cls: 1 occlusion, 2 mismatch; filled: 1 where a value was taken, so a flagged pixel with
+    filled == 0 kept its raw value)."""
+
+    def __init__(self, H, W, D, device):
+        self.H, self.W, self.D, self.device = int(H), int(W), int(D), torch.device(device)
+        self.cls = self.filled = self.ws = None
+
+    @classmethod
+    def make(cls, H, W, D, device, fill):
+        """fill -> None ("mean4") or a stage ("interpolate")."""
+        return cls(H, W, D, device) if ops.fill_mode(fill) == "interpolate" else None
+
+    def run(self, disp_l, disp_r, lrc_l, max_diff, out):
+        """-> out, the left map with its flagged pixels interpolated; lrc_l is left as it is."""
+        H, W, dev = self.H, self.W, self.device
+        if self.ws is None:
+            self.cls = torch.empty((H, W), dtype=torch.uint8, device=dev)
+            self.filled = torch.empty((H, W), dtype=torch.uint8, device=dev)
+            self.ws = torch.empty((ops.interpolate_workspace_bytes(H, W),), dtype=torch.uint8, device=dev)
+        ops.classify(disp_r, lrc_l, self.D, "left", max_diff, out=self.cls)
+        ops.interpolate(disp_l, self.cls, "left", out=out, filled=self.filled, workspace=self.ws)
+        return out
+
+
 def run_tower(img_pad, packed, nlayers, out, ws, precision="f16x3", nf=64, combine=None, on_launch=None):
     """Drive tower_steps to the end; combine(words) is applied at every yield (e.g. an all-reduce)."""
     for _stage, words in tower_steps(img_pad, packed, nlayers, out, ws, precision, nf, on_launch):
@@ -141,8 +170,11 @@ class StereoMatcher:
                  nf: int = 64, device=None, d_range=None, sgm: bool = False, tower_precision: str = "f16x3",
                  cv_mode: str = "certified", cbca_iters: int = 0, cbca_L1: int = 14, cbca_tau: float = 0.02,
                  emit_split: bool = False, sgm_placement_trials: int = SGM_PLACEMENT_TRIALS,
-                 subpixel: bool = False, bilateral: bool = False, speckle=None, unique=None):
+                 subpixel: bool = False, bilateral: bool = False, speckle=None, unique=None, fill: str = "mean4"):
         self.H, self.W, self.D = int(height), int(width), int(ndisp)
+        # fill="interpolate": the checked paths (match_lr, sgm_path with post=True) classify the flagged left pixels
+        # and interpolate them (include/sde_interp.h) where "mean4" (the default) runs the reference's LRC fill
+        self.fill = ops.fill_mode(fill)
         # unique=tau: the uniqueness check (include/sde_unique.h) inside the fused CV + WTA of match() / match_lr()
         # and on the SGM path's S volumes; None (the default) leaves every path's launches and allocations as they are
         self.unique = None if unique is None else ops.unique_tau(unique)
@@ -209,7 +241,7 @@ class StereoMatcher:
         # the z-normalised images
         self.sgm = SgmPath(H, W, self.D, dev, self.cbca_iters, self.cbca_L1, self.cbca_tau, self.subpixel,
                            self.bilateral, self.sgm_placement_trials, scratch=(self.img_pad, self.stats, L),
-                           speckle=self.speckle, unique=self.unique)
+                           speckle=self.speckle, unique=self.unique, fill=self.fill)
         if sgm:
             self.sgm.alloc()
 
@@ -351,7 +383,7 @@ class StereoMatcher:
             self.argmin_r = torch.empty((H, W), dtype=torch.int32, device=dev)
             self.cv_ws_r = torch.empty(ops.cv_wta_workspace_bytes(H, W), dtype=torch.uint8, device=dev)
             self.reject_r = torch.empty((H, W), dtype=torch.uint8, device=dev) if self.unique is not None else None
-            self.checked = CheckedPath(H, W, dev, self.bilateral, self.speckle)
+            self.checked = CheckedPath(H, W, dev, self.bilateral, self.speckle, self.fill, self.D)
             self.lr_bufs = self.checked.bufs
         return self.lr_bufs
 
@@ -383,7 +415,9 @@ class StereoMatcher:
         image (the reference's dead call, :1260, would filter the LRC-filled map and overwrite the median's
         result: a documented divergence); speckle removal, when set, comes last.  With
         unique=tau both views come from the fused unique form: a rejected pixel is -1 in its raw map, which the
-        check flags (d < 0), so rejected left pixels are filled by the LRC fill."""
+        check flags (d < 0), so rejected left pixels are filled by the LRC fill.  With fill="interpolate" the
+        flagged left pixels are classified against the right map and interpolated (InterpStage) instead of
+        LRC-filled."""
         self._need_whole_range()
         self._lr_bufs()
         self.cost_wta()
@@ -420,10 +454,14 @@ class CheckedPath:
     process_functional.py:977-1088, :840-879) and the maps it writes: the wrap-free left-right check, LRC fill of
     the left map, 5x5 median and, with bilateral=True, the 9x9 bilateral filter of the median's output; with
     speckle=(max_size, max_diff) (or a SpeckleStage to share) speckle removal of the map that would be returned.
-    Shared by StereoMatcher.lr_checked and LocalMatcher.match_lr."""
+    fill="interpolate" (with ndisp, the matcher's D): the flagged left pixels are classified and interpolated
+    (InterpStage) instead of LRC-filled.  Shared by StereoMatcher.lr_checked and LocalMatcher.match_lr."""
 
-    def __init__(self, H, W, device, bilateral: bool = False, speckle=None):
+    def __init__(self, H, W, device, bilateral: bool = False, speckle=None, fill: str = "mean4", ndisp=None):
         self.speckle = SpeckleStage.make(H, W, device, speckle)
+        if ops.fill_mode(fill) == "interpolate" and ndisp is None:
+            raise ValueError("fill='interpolate' needs ndisp, the number of disparities of the two maps")
+        self.interp = InterpStage.make(H, W, ndisp, device, fill)
         f32 = lambda: torch.empty((H, W), dtype=torch.float32, device=device)   # noqa: E731
         u8 = lambda: torch.empty((H, W), dtype=torch.uint8, device=device)      # noqa: E731
         self.bufs = dict(lrc=[u8(), u8()], filled=f32(), checked=f32())
@@ -434,7 +472,10 @@ class CheckedPath:
         """-> (disp_l_checked, disp_r, lrc_l).  img_l: the left u8 image (the bilateral filter's intensities)."""
         b = self.bufs
         ops.lr_consistency(disp_l, disp_r, max_diff, b["lrc"][0], b["lrc"][1])
-        ops.lrc_fill(disp_l, b["lrc"][0], out=b["filled"])
+        if self.interp is not None:
+            self.interp.run(disp_l, disp_r, b["lrc"][0], max_diff, b["filled"])
+        else:
+            ops.lrc_fill(disp_l, b["lrc"][0], out=b["filled"])
         # the 5x5 median of the filled map into the interior of a copy of it: the 2-pixel border keeps the
         # filled values
         b["checked"].copy_(b["filled"])
@@ -457,12 +498,17 @@ class SgmPath:
     two ops.preprocess_scratch_bytes(H, W) scratch tensors (StereoMatcher lends the tower's input buffers).
     subpixel / bilateral: the two stages the reference carries switched off (see run).  unique=tau: the uniqueness
     check on the final S volumes (see run; unique_mask is the left view's decision).  speckle: None, a
-    (max_size, max_diff) pair or a SpeckleStage to share; with post=True the maps run() returns are filtered."""
+    (max_size, max_diff) pair or a SpeckleStage to share; with post=True the maps run() returns are filtered.
+    fill="interpolate": with post=True the flagged left pixels (the uniqueness OR included) are classified and
+    interpolated (InterpStage) where "mean4", the default, runs the LRC fill."""
 
     def __init__(self, height: int, width: int, ndisp: int, device, cbca_iters: int = 0, cbca_L1: int = 14,
                  cbca_tau: float = 0.02, subpixel: bool = False, bilateral: bool = False,
-                 placement_trials: int = SGM_PLACEMENT_TRIALS, scratch=None, speckle=None, unique=None):
+                 placement_trials: int = SGM_PLACEMENT_TRIALS, scratch=None, speckle=None, unique=None,
+                 fill: str = "mean4"):
         self.H, self.W, self.D, self.device = int(height), int(width), int(ndisp), torch.device(device)
+        self.fill = ops.fill_mode(fill)
+        self.interp = InterpStage.make(self.H, self.W, self.D, self.device, fill)
         self.unique = None if unique is None else ops.unique_tau(unique)
         self.cbca_iters, self.cbca_L1, self.cbca_tau = int(cbca_iters), int(cbca_L1), float(cbca_tau)
         self.subpixel, self.bilateral = bool(subpixel), bool(bilateral)
@@ -645,7 +691,11 @@ class SgmPath:
         ops.lr_check(b["disp"][0], b["disp"][1], b["lrc"][0], b["lrc"][1])
         if self.unique is not None:
             b["lrc"][0].bitwise_or_(b["rej"][0])
-        ops.lrc_fill(b["disp"][0], b["lrc"][0], out=b["disp_a"])
+        if self.interp is not None:
+            # the check's own bound is 1 (is_error_match_kernel), so the classification's is too
+            self.interp.run(b["disp"][0], b["disp"][1], b["lrc"][0], 1.0, b["disp_a"])
+        else:
+            ops.lrc_fill(b["disp"][0], b["lrc"][0], out=b["disp_a"])
         t = mark("lrc", t)
         # Median_Filter_kernel(d_disparityl_a, d_disparityr_a, d_disparityl, d_disparityr) (:1250):
         # the interior of disp_l becomes the median of the LRC-filled map.  The reference's

@@ -100,7 +100,7 @@ def add_detail_time(detail_time, timings):
 
 
 def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, ndisp=128, subpixel=False,
-                             bilateral=False, unique=None):
+                             bilateral=False, unique=None, fill="mean4"):
     """GPU path (process_functional.py:1093-1267): cost volume [H,W,D] (L, R; 1.0 fill),
     SGM penalties, 8-path SGM, WTA, LR check + LRC fill, 5x5 median.
 
@@ -109,7 +109,8 @@ def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, 
     ``ndisp`` defaults to the reference's hard-coded 128 (:1111).  ``subpixel`` / ``bilateral`` switch on the two
     stages the reference carries commented out: the parabola step of the WTA kernel (:813-819) and
     Bilateral_Filter_kernel (:882-974), the latter applied to the median's output.  ``unique`` (build-defined, off by
-    default): SgmPath's uniqueness check with that absolute margin.
+    default): SgmPath's uniqueness check with that absolute margin.  ``fill`` (build-defined): "interpolate" classifies
+    and interpolates the flagged left pixels (include/sde_interp.h) where "mean4", the default, is LRC_kernel.
     """
     assert imagel.shape == imager.shape                   # :1097
     H, W = imagel.shape[0:2]
@@ -120,7 +121,7 @@ def disparity_compute_by_gpu(imagel, imager, featuresl, featuresr, detail_time, 
         raise ValueError("features and images differ in size")
     # cbca_iters = 0: the reference has no aggregation stage
     path = SgmPath(H, W, int(ndisp), fl.device, cbca_iters=0, subpixel=subpixel, bilateral=bilateral,
-                   unique=unique)
+                   unique=unique, fill=fill)
     timings = {}
     dl, dr = path.run(fl, fr, il, ir, timings=timings)
     return dl.cpu().numpy(), dr.cpu().numpy(), add_detail_time(detail_time, timings)
